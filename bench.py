@@ -27,6 +27,19 @@ Extra objects on the JSON line:
                 (committed counter passes of the builder's profiling run — NOT measured in this run).
   cpu_baseline  the CPU oracle (oracle/, a port of cpu_engine_kernel; uncalibrated against the reference, which cannot be built here)
                 timed on this host's cores on a bounded sample of the same workload.  Reported baseline only.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs: scene and context set-up, the first pass,
+W warm-up steps, EXACTLY N timed steps between two fences (`--repeats` / `--min-seconds` ask for more), the outputs (`--dump-outputs`) and
+the line.  Everything else — `roofline` (instrumented and counted runs), `end_to_end`, `spp_per_s`, `hosts_default_packaging`,
+`other_shard_mode` and `cpu_baseline` — is measured with `--full` only, which also times the N steps repeatedly by default (at least 5
+repeats and 5 s of timed wall, the line reporting the median repeat).
+
+`--dump-outputs DIR` writes, after the timed steps and before anything else renders, what a caller of the timed path receives from its
+last step, as float32 .npy files: `accum.npy` (the RGBA32F accumulators, [H, W, 4]; rank 0's summed accumulators under sample sharding)
+and `image.npy` (the tone-mapped 8-bit frame's R, G, B as float32, [H, W, 3]; its alpha is always 255).  Frames whose files would pass
+DUMP_BUDGET_BYTES are written as the same fixed, seeded sample of pixels from every array ([n, C], pixel indices y * W + x in
+`sampled_pixel_index.npy`).  Inputs are fixed (scene presets, seed of the render config), so runs with the same arguments compare output
+for output.
 """
 import argparse
 import json
@@ -39,6 +52,7 @@ sys.path.insert(0, ROOT)
 
 RPP = 8
 PEAK_HBM_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); measured copy ceiling ~6.3 TB/s
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files of one run together stay under 64 MB
 
 
 def algorithmic_bytes(c):
@@ -76,18 +90,40 @@ def cpu_baseline(flat, cam, cfg, budget_s=12.0):
                       f"({rays} path segments, {dt:.1f} s) after one warm-up pass"}
 
 
+def dump_outputs(directory, arrays):
+    """arrays: name -> float32 [H, W, C] frame.  Whole frames when all of them fit in DUMP_BUDGET_BYTES, else the same fixed, seeded sample
+    of pixels from each ([n, C]) and the sampled pixel indices."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    h, w = next(iter(arrays.values())).shape[:2]
+    n_pix = h * w
+    per_pixel = sum(a.nbytes // n_pix for a in arrays.values())
+    if n_pix * per_pixel > DUMP_BUDGET_BYTES - 4096:   # (headroom for the .npy headers)
+        per_pixel += 8   # the float64 index of every sampled pixel
+        idx = np.sort(np.random.default_rng(0).choice(n_pix, size=(DUMP_BUDGET_BYTES - 4096) // per_pixel, replace=False))
+        arrays = {name: a.reshape(n_pix, -1)[idx] for name, a in arrays.items()}
+        arrays["sampled_pixel_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40, help="steps per timed repeat (each step = 8 passes: >= 64 passes per repeat from 8 steps on)")
+    ap.add_argument("--steps", type=int, default=40, help="timed steps (each step = 8 passes): a plain run times exactly these steps, once")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="the K timed steps are repeated at least this many times; the line reports the median repeat")
-    ap.add_argument("--min-seconds", type=float, default=5.0, help="keep repeating the K timed steps until the repeats add up to this much timed wall (SURVEY.md 8d: >= 5 s)")
+    ap.add_argument("--repeats", type=int, default=None, help="time the K steps at least this many times; the line reports the median repeat (default 1; 5 with --full)")
+    ap.add_argument("--min-seconds", type=float, default=None, help="keep repeating the K timed steps until the repeats add up to this much timed wall (default 0; 5 with --full, SURVEY.md 8d: >= 5 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (per-kernel events, counted runs), end_to_end, spp_per_s, "
+                         "hosts_default_packaging, other_shard_mode (N > 1) and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what their last step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--config", default="B", help="scene preset of rayzath_amd/scenes.py (B = the quoted config)")
     ap.add_argument("--shard-mode", default="auto", choices=["auto", "samples", "tiles"],
                     help="how N > 1 GPUs divide the frame: samples = whole frame per rank on its own seed stream + one reduce(sum) of the accumulators per step; "
                          "tiles = interleaved 32x8 tiles + one gather per step; auto = samples (tile sharding's kernel-side speed-up is capped by its slowest tile's chain of passes, DESIGN.md §7)")
-    ap.add_argument("--no-other-mode", action="store_true", help="N > 1: do not measure the other shard mode beside the chosen one")
+    ap.add_argument("--no-other-mode", action="store_true", help="--full, N > 1: do not measure the other shard mode beside the chosen one")
     ap.add_argument("--traversal", type=int, default=-1, help="-1 per-scene choice (default), 1 nested walk with LDS stack, 2 workgroup-binned, 3 skip links (front to back, cooperative triangle phase)")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: collective on the render stream instead of overlapping it with the next step's rendering")
     ap.add_argument("--pipeline", type=int, default=-1, help="0 fused pass kernel, 1 trace + shade kernels, 2 resident batch kernel (-1: chosen per scene)")
@@ -97,11 +133,15 @@ def main():
     ap.add_argument("--mode", type=int, default=0, help="hiprz_set_mode flags: 0 = the CPU kernel (the parity-checked default), 63 = every behaviour of the reference's CUDA engine")
     ap.add_argument("--tree", type=int, default=4, help="hiprz_set_tree: 4 the Engine hosts' default (the scene's own trees when it is staged in LDS, else built on the device with a binned SAH), 0 the scene's (reference) mesh trees, 1 rebuilt on the host with a binned SAH, 2 / 3 built on the device in Morton order / with a binned SAH; frames are the same under all of them")
     ap.add_argument("--no-xcd-swizzle", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: do not time the CPU oracle")
     ap.add_argument("--verify-gather", action="store_true", help="N > 1: check the assembled frame — tiles: against an unsharded render, bit for bit; samples: against the sum of one-GPU renders on the ranks' seeds")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N ranks share GPU 0 and talk over gloo: exercises the sharded path where only one GPU exists")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.min_seconds is None:
+        args.min_seconds = 5.0 if args.full else 0.0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` as typed: this process touches no GPU — it starts one rank per GPU (torch.distributed.run, the
@@ -229,7 +269,7 @@ def main():
 
     def measure(k_streams, mode, keep=False):
         """One packaging through the whole protocol: context(s) -> first pass -> warm-up -> timed repeats.  Returns the figures (and, with
-        `keep`, the context for the roofline's instrumented runs)."""
+        `keep`, the context for the roofline's instrumented runs and the frame for the outputs)."""
         ctx = make_context([local_rank] * k_streams if k_streams > 1 else local_rank, mode)
         frame = ShardedFrame(ctx, rank, world, W, H, dist if world > 1 else None, device, overlap=not args.no_overlap, mode=mode)
 
@@ -249,13 +289,13 @@ def main():
             step()
         fence(ctx)
         ctx.kernel_time_ms()  # drop the warm-up launches from the event log
-        alpha_before = float(ctx.read_accum()[..., 3].sum()) if rank == 0 and world == 1 else None
+        alpha_before = float(ctx.read_accum()[..., 3].sum()) if args.full and rank == 0 and world == 1 else None
         passes_before = ctx.pass_count()
         t_all0 = time.perf_counter()
         samples = timed_repeats(ctx, step)
         timed_wall = time.perf_counter() - t_all0
         elapsed = sorted(samples)[len(samples) // 2]
-        kernel_ms, launches = ctx.kernel_time_ms()   # hip events around every render batch of the timed repeats (head stream)
+        kernel_ms, launches = ctx.kernel_time_ms() if args.full else (None, None)   # hip events around every render batch of the timed repeats (head stream)
         alpha_after = float(ctx.read_accum()[..., 3].sum()) if alpha_before is not None else None
         rays_per_step = RPP * W * H * (world if mode == "samples" else 1)
         out = {"streams": k_streams, "shard_mode": mode if world > 1 else "single GPU", "value": args.steps * rays_per_step / elapsed / 1e6, "unit": "Mrays/s",
@@ -264,146 +304,158 @@ def main():
                "passes_timed": ctx.pass_count() - passes_before, "timed_wall_seconds": timed_wall, "kernel_ms": kernel_ms, "launches": launches,
                "spp_per_s": (alpha_after - alpha_before) / (W * H) / sum(samples) if alpha_before is not None else None}
         if keep:
-            return out, ctx
+            return out, ctx, frame
         fence(ctx)
         ctx.close()
-        return out, None
+        return out, None, None
 
     # ---- the line's packaging: one context, one stream per GPU
-    main_run, ctx = measure(1, shard_mode, keep=True)
-    elapsed_step_s = main_run["ms_per_step"] / 1e3
+    main_run, ctx, frame = measure(1, shard_mode, keep=True)
     kernel_ms, launches = main_run["kernel_ms"], main_run["launches"]
 
-    # ---- outside the timed region: per-kernel events (eager launches), host readback, work counters
-    ctx.time_kernels(True)
-    trace_ms = shade_ms = 0.0
-    timed_passes = 0
-    for _ in range(3):
-        ctx.render(RPP)
-        b = ctx.kernel_breakdown_ms()
-        trace_ms, shade_ms, timed_passes = trace_ms + b[0], shade_ms + b[1], timed_passes + b[2]
-    ctx.time_kernels(False)
-    breakdown = (trace_ms, shade_ms, timed_passes)
-    ctx.kernel_time_ms()
-    end_to_end = None
-    if world == 1:  # what the reference's renderWorld hands back per call: the tone-mapped frame in host memory
-        ctx.render(RPP), ctx.tonemap(), ctx.read_rgba8()
+    # ---- what the last timed step computed, before anything else renders into the context
+    if args.dump_outputs:
+        frame.sync()
         fence(ctx)
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            ctx.render(RPP)
-            ctx.tonemap()
-            ctx.read_rgba8()
-        fence(ctx)
-        e2e = time.perf_counter() - t0
-        end_to_end = {"value": args.steps * RPP * W * H / e2e / 1e6, "unit": "Mrays/s", "ms_per_step": e2e / args.steps * 1e3,
-                      "includes": "render + tone map + hiprz_read_rgba8 into host memory (8.3 MB per step over PCIe, synchronous)"}
-        ctx.kernel_time_ms()
+        outputs = None
+        if world == 1:
+            outputs = {"accum": ctx.read_accum(), "image": ctx.read_rgba8()[..., :3].astype(np.float32)}
+        elif rank == 0:   # the frame the job assembles on rank 0: summed accumulators + their tone map (samples), the gathered tone map (tiles)
+            image = frame.rgba8.cpu().numpy().view(np.uint8).reshape(H, W, 4)[..., :3].astype(np.float32)
+            outputs = {"accum": frame.image.cpu().numpy(), "image": image} if shard_mode == "samples" else {"image": image}
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
 
-    # ---- the hosts' default packaging (rayzath_amd.engine.default_streams, Hip::Engine::defaultStreams): the rank's share over K streams on its
-    # GPU (hiprz_create_multi with the device named K times: tiles interleaved, ONE scene copy shared) — one stream's sorts, pass bookkeeping
-    # and kernel tails run beside another's walks.  Same protocol, same shard mode and collective.
-    hosts_default = None
-    k_streams = args.streams if args.streams > 0 else default_streams(len(flat.spot_lights) + len(flat.direct_lights))
-    if k_streams > 1:
-        fence(ctx)
-        hosts_default, _ = measure(k_streams, shard_mode)
-        for k in ("kernel_ms", "launches", "spp_per_s", "passes_timed", "timed_wall_seconds"):
-            hosts_default.pop(k)
-        hosts_default["note"] = ("same steps, same protocol; every rank's share interleaved over %d contexts on its GPU, each with its own stream, one scene copy "
-                                 "(what Hip::Engine / rayzath_amd.engine.Engine do by default for scenes without lights)" % k_streams)
-    # ---- N > 1: the other way to divide the frame, one stream per GPU, same protocol
-    other_mode = None
-    if world > 1 and not args.no_other_mode:
-        fence(ctx)
-        other_mode, _ = measure(1, "tiles" if shard_mode == "samples" else "samples")
-        for k in ("kernel_ms", "launches", "spp_per_s", "passes_timed", "timed_wall_seconds"):
-            other_mode.pop(k)
+    breakdown = end_to_end = hosts_default = other_mode = None
+    if args.full:
+        # ---- outside the timed region: per-kernel events (eager launches), host readback, work counters
+        ctx.time_kernels(True)
+        trace_ms = shade_ms = 0.0
+        timed_passes = 0
+        for _ in range(3):
+            ctx.render(RPP)
+            b = ctx.kernel_breakdown_ms()
+            trace_ms, shade_ms, timed_passes = trace_ms + b[0], shade_ms + b[1], timed_passes + b[2]
+        ctx.time_kernels(False)
+        breakdown = (trace_ms, shade_ms, timed_passes)
+        ctx.kernel_time_ms()
+        if world == 1:  # what the reference's renderWorld hands back per call: the tone-mapped frame in host memory
+            ctx.render(RPP), ctx.tonemap(), ctx.read_rgba8()
+            fence(ctx)
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                ctx.render(RPP)
+                ctx.tonemap()
+                ctx.read_rgba8()
+            fence(ctx)
+            e2e = time.perf_counter() - t0
+            end_to_end = {"value": args.steps * RPP * W * H / e2e / 1e6, "unit": "Mrays/s", "ms_per_step": e2e / args.steps * 1e3,
+                          "includes": "render + tone map + hiprz_read_rgba8 into host memory (8.3 MB per step over PCIe, synchronous)"}
+            ctx.kernel_time_ms()
+
+        # ---- the hosts' default packaging (rayzath_amd.engine.default_streams, Hip::Engine::defaultStreams): the rank's share over K streams on its
+        # GPU (hiprz_create_multi with the device named K times: tiles interleaved, ONE scene copy shared) — one stream's sorts, pass bookkeeping
+        # and kernel tails run beside another's walks.  Same protocol, same shard mode and collective.
+        k_streams = args.streams if args.streams > 0 else default_streams(len(flat.spot_lights) + len(flat.direct_lights))
+        if k_streams > 1:
+            fence(ctx)
+            hosts_default, _, _ = measure(k_streams, shard_mode)
+            for k in ("kernel_ms", "launches", "spp_per_s", "passes_timed", "timed_wall_seconds"):
+                hosts_default.pop(k)
+            hosts_default["note"] = ("same steps, same protocol; every rank's share interleaved over %d contexts on its GPU, each with its own stream, one scene copy "
+                                     "(what Hip::Engine / rayzath_amd.engine.Engine do by default for scenes without lights)" % k_streams)
+        # ---- N > 1: the other way to divide the frame, one stream per GPU, same protocol
+        if world > 1 and not args.no_other_mode:
+            fence(ctx)
+            other_mode, _, _ = measure(1, "tiles" if shard_mode == "samples" else "samples")
+            for k in ("kernel_ms", "launches", "spp_per_s", "passes_timed", "timed_wall_seconds"):
+                other_mode.pop(k)
 
     if rank == 0:
-        # work counters of the same kernels, same state
-        counters = ctx.render_counted(RPP)
-        ctx.kernel_time_ms()
-        bytes_per_pass = algorithmic_bytes(counters) / RPP
-        avg_pass_s = kernel_ms / 1e3 / max(launches, 1)
         pipeline = ctx.pipeline()
         split = pipeline == 1
         walk_order = args.walk_order if args.walk_order >= 0 else 1
-        front_to_back = split and ctx.traversal_mode() == 3 and (walk_order != 0 or bool(args.mode & 31))
-        trace_bytes = lambda c: (60 * c["segments"] + 32 * (c["box_tests"] - c["shadow_box_tests"]) + 36 * (c["tri_tests"] - c["shadow_tri_tests"])) / RPP
-        traversal_kernel = eager_kernel_us = None
-        if pipeline == 2 and breakdown[2]:
-            # dominant (only) kernel: the resident batch kernel — one launch takes every tile through the RPP passes of the
-            # step.  Algorithmic bytes: SURVEY.md §8d's per-segment figure x the segments of the launch.
-            # (scenes staged in LDS: rz_batch_kernel, a workgroup per tile, the reference's visiting order; scenes that are not: rz_wave_batch_kernel,
-            # a wave per 8x8 pixels on the cooperative front-to-back walk — `counters` are then the tests that walk executes)
-            kernel_name = "rz_batch_kernel (resident: all passes of a step)" if ctx.traversal_mode() != 3 else "rz_wave_batch_kernel (per-wave resident: all passes of a step)"
-            # duration: the hip events the context records on its stream around EVERY render batch of the timed repeats (the batch
-            # kernel + the one-thread kernel that advances the pass index) — the launches `value` was timed on, not a separate run
-            kernel_s = kernel_ms / 1e3 / max(launches // RPP, 1)
-            eager_kernel_us = breakdown[0] / (breakdown[2] / RPP) * 1e3  # the same kernel between its own two events, after the timed region
-            kernel_bytes = algorithmic_bytes(counters)
-            # the BVH-traversal kernel on its own (north_star's 30 % target): the same step through the split pipeline
-            ctx.set_pipeline(1)
-            ctx.render(RPP)
-            ctx.time_kernels(True)
-            ctx.render(RPP)
-            tb = ctx.kernel_breakdown_ms()
-            ctx.time_kernels(False)
-            ctx.set_pipeline(args.pipeline)
-            if tb[2]:
-                t_bytes = trace_bytes(counters)
-                t_s = tb[0] / 1e3 / tb[2]
-                traversal_kernel = {"kernel": "rz_trace_kernel (closest-hit walk, split pipeline)", "avg_launch_us": t_s * 1e6,
-                                    "algorithmic_bytes_per_launch": t_bytes, "achieved": t_bytes / t_s / 1e9,
-                                    "frac": t_bytes / t_s / 1e9 / PEAK_HBM_GBS, "shade_kernel_avg_launch_us": tb[1] / tb[2] * 1e3}
-        elif split and breakdown[2]:
-            # dominant kernel = the BVH-traversal kernel.  Its algorithmic bytes: the ray it reads (40 B of path state) and
-            # the hit record it writes (20 B) per segment + 32 B per box test + 36 B per triangle test of the closest-hit
-            # walk (shadow-ray tests run in their own kernel and are not counted here).
-            mode3 = ("rz_trace_coop_compat_kernel" if args.mode & 31 else "rz_trace_coop_kernel") if front_to_back else "rz_trace_skip_kernel"
-            kernel_name = {3: mode3}.get(ctx.traversal_mode(), "rz_trace_kernel") + " (closest-hit walk)"
-            kernel_s = breakdown[0] / 1e3 / breakdown[2]
-            kernel_bytes = trace_bytes(counters)
-            if front_to_back and not (args.mode & 31):
-                # `counters` walked in the reference's child order.  The timed kernel walks front to back and reaches the same hits with
-                # fewer tests: the roofline is priced on the tests it EXECUTED.
-                ctx.set_walk_order(2)
-                counters = ctx.render_counted(RPP)
-                ctx.set_walk_order(walk_order)
-                ctx.kernel_time_ms()
+        if args.full:
+            # work counters of the same kernels, same state
+            counters = ctx.render_counted(RPP)
+            ctx.kernel_time_ms()
+            bytes_per_pass = algorithmic_bytes(counters) / RPP
+            avg_pass_s = kernel_ms / 1e3 / max(launches, 1)
+            front_to_back = split and ctx.traversal_mode() == 3 and (walk_order != 0 or bool(args.mode & 31))
+            trace_bytes = lambda c: (60 * c["segments"] + 32 * (c["box_tests"] - c["shadow_box_tests"]) + 36 * (c["tri_tests"] - c["shadow_tri_tests"])) / RPP
+            traversal_kernel = eager_kernel_us = None
+            if pipeline == 2 and breakdown[2]:
+                # dominant (only) kernel: the resident batch kernel — one launch takes every tile through the RPP passes of the
+                # step.  Algorithmic bytes: SURVEY.md §8d's per-segment figure x the segments of the launch.
+                # (scenes staged in LDS: rz_batch_kernel, a workgroup per tile, the reference's visiting order; scenes that are not: rz_wave_batch_kernel,
+                # a wave per 8x8 pixels on the cooperative front-to-back walk — `counters` are then the tests that walk executes)
+                kernel_name = "rz_batch_kernel (resident: all passes of a step)" if ctx.traversal_mode() != 3 else "rz_wave_batch_kernel (per-wave resident: all passes of a step)"
+                # duration: the hip events the context records on its stream around EVERY render batch of the timed repeats (the batch
+                # kernel + the one-thread kernel that advances the pass index) — the launches `value` was timed on, not a separate run
+                kernel_s = kernel_ms / 1e3 / max(launches // RPP, 1)
+                eager_kernel_us = breakdown[0] / (breakdown[2] / RPP) * 1e3  # the same kernel between its own two events, after the timed region
+                kernel_bytes = algorithmic_bytes(counters)
+                # the BVH-traversal kernel on its own (north_star's 30 % target): the same step through the split pipeline
+                ctx.set_pipeline(1)
+                ctx.render(RPP)
+                ctx.time_kernels(True)
+                ctx.render(RPP)
+                tb = ctx.kernel_breakdown_ms()
+                ctx.time_kernels(False)
+                ctx.set_pipeline(args.pipeline)
+                if tb[2]:
+                    t_bytes = trace_bytes(counters)
+                    t_s = tb[0] / 1e3 / tb[2]
+                    traversal_kernel = {"kernel": "rz_trace_kernel (closest-hit walk, split pipeline)", "avg_launch_us": t_s * 1e6,
+                                        "algorithmic_bytes_per_launch": t_bytes, "achieved": t_bytes / t_s / 1e9,
+                                        "frac": t_bytes / t_s / 1e9 / PEAK_HBM_GBS, "shade_kernel_avg_launch_us": tb[1] / tb[2] * 1e3}
+            elif split and breakdown[2]:
+                # dominant kernel = the BVH-traversal kernel.  Its algorithmic bytes: the ray it reads (40 B of path state) and
+                # the hit record it writes (20 B) per segment + 32 B per box test + 36 B per triangle test of the closest-hit
+                # walk (shadow-ray tests run in their own kernel and are not counted here).
+                mode3 = ("rz_trace_coop_compat_kernel" if args.mode & 31 else "rz_trace_coop_kernel") if front_to_back else "rz_trace_skip_kernel"
+                kernel_name = {3: mode3}.get(ctx.traversal_mode(), "rz_trace_kernel") + " (closest-hit walk)"
+                kernel_s = breakdown[0] / 1e3 / breakdown[2]
                 kernel_bytes = trace_bytes(counters)
-        else:
-            kernel_name, kernel_s, kernel_bytes = "rz_pass_kernel (fused pass)", avg_pass_s, bytes_per_pass
-        # the reference ALGORITHM's work on the same scene: first-child-then-second walks of the snapshot's (reference) trees — a bare
-        # context (HIPRZ_TREE_REFERENCE, walk order 0), whatever trees and order the timed context uses
-        reference_algorithm = None
-        if world == 1 and not (args.mode & 31):
-            bare = Context(local_rank)
-            bare.set_walk_order(0)
-            bare.upload_scene(flat), bare.upload_camera(cam), bare.set_config(cfg)
-            bare.render(1)
-            rc = bare.render_counted(RPP)
-            bare.close()
-            ref_bytes = trace_bytes(rc) if split else algorithmic_bytes(rc)
-            reference_algorithm = {"note": "work of the reference's first-child-then-second walk of the snapshot's (reference builder's) trees over passes 2..9 of the same frame, divided by the timed kernel's duration",
-                                   "box_tests_per_segment": rc["box_tests"] / max(rc["segments"], 1), "tri_tests_per_segment": rc["tri_tests"] / max(rc["segments"], 1),
-                                   "kernel_bytes_per_launch": ref_bytes, "achieved": ref_bytes / kernel_s / 1e9, "frac": ref_bytes / kernel_s / 1e9 / PEAK_HBM_GBS}
-        achieved = kernel_bytes / kernel_s / 1e9
-        # HBM bytes and SQ figures of the same kernel: counter passes of the builder's profiling run of this command, committed under
-        # profiles/ (tools/round_profiles.sh) — replayed here, not measured in this run
-        traffic, compute, counters_from = None, {}, None
-        tpath, spath = os.path.join(ROOT, "profiles", f"traffic_{args.config}.json"), os.path.join(ROOT, "profiles", f"sq_{args.config}.json")
-        short = kernel_name.split(" ")[0]
-        if world == 1 and os.path.exists(tpath):
-            traffic = json.load(open(tpath)).get(short, {}).get("hbm_bytes_per_launch")
-        if world == 1 and os.path.exists(spath):
-            compute = json.load(open(spath)).get(short, {})
-        if traffic is not None or compute:
-            meta = json.load(open(spath)).get("_meta", {}) if os.path.exists(spath) else {}
-            counters_from = (f"profiles/sq_{args.config}.json, profiles/traffic_{args.config}.json: rocprofv3 --pmc passes of `bench.py --config {args.config} --streams 1` "
-                             f"run by the builder ({meta.get('collected', 'round 3')}), committed and replayed here — NOT measured in this run")
-        valu_bound = bool(compute.get("valu_busy"))
+                if front_to_back and not (args.mode & 31):
+                    # `counters` walked in the reference's child order.  The timed kernel walks front to back and reaches the same hits with
+                    # fewer tests: the roofline is priced on the tests it EXECUTED.
+                    ctx.set_walk_order(2)
+                    counters = ctx.render_counted(RPP)
+                    ctx.set_walk_order(walk_order)
+                    ctx.kernel_time_ms()
+                    kernel_bytes = trace_bytes(counters)
+            else:
+                kernel_name, kernel_s, kernel_bytes = "rz_pass_kernel (fused pass)", avg_pass_s, bytes_per_pass
+            # the reference ALGORITHM's work on the same scene: first-child-then-second walks of the snapshot's (reference) trees — a bare
+            # context (HIPRZ_TREE_REFERENCE, walk order 0), whatever trees and order the timed context uses
+            reference_algorithm = None
+            if world == 1 and not (args.mode & 31):
+                bare = Context(local_rank)
+                bare.set_walk_order(0)
+                bare.upload_scene(flat), bare.upload_camera(cam), bare.set_config(cfg)
+                bare.render(1)
+                rc = bare.render_counted(RPP)
+                bare.close()
+                ref_bytes = trace_bytes(rc) if split else algorithmic_bytes(rc)
+                reference_algorithm = {"note": "work of the reference's first-child-then-second walk of the snapshot's (reference builder's) trees over passes 2..9 of the same frame, divided by the timed kernel's duration",
+                                       "box_tests_per_segment": rc["box_tests"] / max(rc["segments"], 1), "tri_tests_per_segment": rc["tri_tests"] / max(rc["segments"], 1),
+                                       "kernel_bytes_per_launch": ref_bytes, "achieved": ref_bytes / kernel_s / 1e9, "frac": ref_bytes / kernel_s / 1e9 / PEAK_HBM_GBS}
+            achieved = kernel_bytes / kernel_s / 1e9
+            # HBM bytes and SQ figures of the same kernel: counter passes of the builder's profiling run of this command, committed under
+            # profiles/ (tools/round_profiles.sh) — replayed here, not measured in this run
+            traffic, compute, counters_from = None, {}, None
+            tpath, spath = os.path.join(ROOT, "profiles", f"traffic_{args.config}.json"), os.path.join(ROOT, "profiles", f"sq_{args.config}.json")
+            short = kernel_name.split(" ")[0]
+            if world == 1 and os.path.exists(tpath):
+                traffic = json.load(open(tpath)).get(short, {}).get("hbm_bytes_per_launch")
+            if world == 1 and os.path.exists(spath):
+                compute = json.load(open(spath)).get(short, {})
+            if traffic is not None or compute:
+                meta = json.load(open(spath)).get("_meta", {}) if os.path.exists(spath) else {}
+                counters_from = (f"profiles/sq_{args.config}.json, profiles/traffic_{args.config}.json: rocprofv3 --pmc passes of `bench.py --config {args.config} --streams 1` "
+                                 f"run by the builder ({meta.get('collected', 'round 3')}), committed and replayed here — NOT measured in this run")
+            valu_bound = bool(compute.get("valu_busy"))
         result = {
             "metric": "Mrays/s (path segments, primary+secondary) at 1920x1080 depth 8" if args.config == "B" else f"Mrays/s config {args.config}",
             "value": main_run["value"], "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -421,42 +473,46 @@ def main():
                        "pipeline": {0: "fused (one kernel per pass)", 1: "trace+shade (two kernels per pass)", 2: "resident (one kernel per step)"}[pipeline]},
             "shard_mode": main_run["shard_mode"], "streams_per_gpu": 1, "rays_per_step": main_run["rays_per_step"],
             "value_from": "one context, one stream per GPU: whole-share launches — the packaging `roofline` and `timing` describe too",
-            "timing": {"protocol": f"{main_run['repeats']} repeats of exactly {args.steps} steps ({args.steps * RPP} passes per GPU) between barrier + synchronize fences (repeated until >= {args.min_seconds:g} s of timed wall); value = median repeat",
+            "timing": {"protocol": (f"exactly {args.steps} steps ({args.steps * RPP} passes per GPU) between barrier + synchronize fences, timed once" if main_run["repeats"] == 1 else
+                                    f"{main_run['repeats']} repeats of exactly {args.steps} steps ({args.steps * RPP} passes per GPU) between barrier + synchronize fences (repeated until >= {args.min_seconds:g} s of timed wall); value = median repeat"),
                        "repeat_seconds_min_median_max": main_run["repeat_seconds_min_median_max"], "repeats": main_run["repeats"], "timed_seconds": main_run["timed_seconds"],
                        "passes_timed": main_run["passes_timed"], "timed_wall_seconds": main_run["timed_wall_seconds"]},
-            "spp_per_s": main_run["spp_per_s"],
-            "end_to_end": end_to_end,
-            "hosts_default_packaging": hosts_default,
-            "other_shard_mode": other_mode,
-            "roofline": {"bound": "valu-issue" if valu_bound else "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": achieved / PEAK_HBM_GBS,
-                         "traffic": traffic, "kernel": kernel_name, "avg_launch_us": kernel_s * 1e6,
-                         "roofline_priced": "hbm (SURVEY.md §8d: algorithmic bytes of the launch / its duration / 8 TB/s); `traffic` is what physically crossed HBM per launch",
-                         "valu_busy": compute.get("valu_busy"), "lanes_active": compute.get("lanes_active"),
-                         "valu_instr_per_wave": compute.get("valu_instr_per_wave"),
-                         "bound_measured": "vector-instruction issue: valu_busy of the chip's VALU issue capacity at lanes_active of the lanes (SQ counters); the algorithmic bytes of a scene that lives in LDS / L2 never reach HBM" if valu_bound else None,
-                         "counters_from": counters_from,
-                         "duration_from": ("hip events around every render batch of the timed repeats (%d launches)" % (launches // RPP)) if pipeline == 2 else
-                                          "hip events around the kernel in an eager, event-instrumented batch after the timed region (a captured graph cannot be timed from inside)",
-                         "eager_avg_launch_us": eager_kernel_us,
-                         "algorithmic_bytes_per_launch": kernel_bytes,
-                         "priced_on": "tests executed by the timed kernel" + (" (front-to-back walk)" if front_to_back else ""),
-                         "segments_per_launch": counters["segments"] / (1 if pipeline == 2 else RPP),
-                         "traversal_kernel": traversal_kernel,
-                         "shade_kernel_avg_launch_us": breakdown[1] / breakdown[2] * 1e3 if split and breakdown[2] else None,
-                         "whole_pass": {"avg_us": avg_pass_s * 1e6, "algorithmic_bytes": bytes_per_pass,
-                                        "achieved": bytes_per_pass / avg_pass_s / 1e9, "frac": bytes_per_pass / avg_pass_s / 1e9 / PEAK_HBM_GBS,
-                                        "note": "all kernels of a pass; bytes of the executed walks (closest-hit + shadow rays + shading)"},
-                         "box_tests_per_segment": counters["box_tests"] / max(counters["segments"], 1),
-                         "tri_tests_per_segment": counters["tri_tests"] / max(counters["segments"], 1),
-                         "mesh_walk_order": None if not (split and ctx.traversal_mode() == 3) else ("front to back" if walk_order else "reference child order"),
-                         "reference_algorithm": reference_algorithm},
         }
-        # the line's own cross-check: the dominant kernel's launches of a step fit into the step they are part of
-        per_step_us = result["roofline"]["avg_launch_us"] * (1 if pipeline == 2 else RPP)
-        result["roofline"]["dominant_kernel_us_per_step"] = per_step_us
-        result["roofline"]["fits_in_step"] = bool(per_step_us <= result["ms_per_step"] * 1e3 * 1.01)
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(flat, cam, cfg)
+        if args.full:
+            result.update({
+                "spp_per_s": main_run["spp_per_s"],
+                "end_to_end": end_to_end,
+                "hosts_default_packaging": hosts_default,
+                "other_shard_mode": other_mode,
+                "roofline": {"bound": "valu-issue" if valu_bound else "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": achieved / PEAK_HBM_GBS,
+                             "traffic": traffic, "kernel": kernel_name, "avg_launch_us": kernel_s * 1e6,
+                             "roofline_priced": "hbm (SURVEY.md §8d: algorithmic bytes of the launch / its duration / 8 TB/s); `traffic` is what physically crossed HBM per launch",
+                             "valu_busy": compute.get("valu_busy"), "lanes_active": compute.get("lanes_active"),
+                             "valu_instr_per_wave": compute.get("valu_instr_per_wave"),
+                             "bound_measured": "vector-instruction issue: valu_busy of the chip's VALU issue capacity at lanes_active of the lanes (SQ counters); the algorithmic bytes of a scene that lives in LDS / L2 never reach HBM" if valu_bound else None,
+                             "counters_from": counters_from,
+                             "duration_from": ("hip events around every render batch of the timed repeats (%d launches)" % (launches // RPP)) if pipeline == 2 else
+                                              "hip events around the kernel in an eager, event-instrumented batch after the timed region (a captured graph cannot be timed from inside)",
+                             "eager_avg_launch_us": eager_kernel_us,
+                             "algorithmic_bytes_per_launch": kernel_bytes,
+                             "priced_on": "tests executed by the timed kernel" + (" (front-to-back walk)" if front_to_back else ""),
+                             "segments_per_launch": counters["segments"] / (1 if pipeline == 2 else RPP),
+                             "traversal_kernel": traversal_kernel,
+                             "shade_kernel_avg_launch_us": breakdown[1] / breakdown[2] * 1e3 if split and breakdown[2] else None,
+                             "whole_pass": {"avg_us": avg_pass_s * 1e6, "algorithmic_bytes": bytes_per_pass,
+                                            "achieved": bytes_per_pass / avg_pass_s / 1e9, "frac": bytes_per_pass / avg_pass_s / 1e9 / PEAK_HBM_GBS,
+                                            "note": "all kernels of a pass; bytes of the executed walks (closest-hit + shadow rays + shading)"},
+                             "box_tests_per_segment": counters["box_tests"] / max(counters["segments"], 1),
+                             "tri_tests_per_segment": counters["tri_tests"] / max(counters["segments"], 1),
+                             "mesh_walk_order": None if not (split and ctx.traversal_mode() == 3) else ("front to back" if walk_order else "reference child order"),
+                             "reference_algorithm": reference_algorithm},
+            })
+            # the line's own cross-check: the dominant kernel's launches of a step fit into the step they are part of
+            per_step_us = result["roofline"]["avg_launch_us"] * (1 if pipeline == 2 else RPP)
+            result["roofline"]["dominant_kernel_us_per_step"] = per_step_us
+            result["roofline"]["fits_in_step"] = bool(per_step_us <= result["ms_per_step"] * 1e3 * 1.01)
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(flat, cam, cfg)
         print(json.dumps(result), flush=True)
     ctx.close()
     if world > 1:

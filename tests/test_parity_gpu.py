@@ -381,6 +381,47 @@ def test_sharded_bench_path_rehearsal(built):
     assert res["n_gpus"] == 2 and res["value"] > 0 and res["scaling"] == "strong"
 
 
+def test_plain_bench_run_times_its_steps_and_dumps_their_frame(built, tmp_path):
+    """bench.py --gpus 1 --steps N as the driver types it: exactly N timed steps once, the headline keys and none of --full's figures;
+    --dump-outputs writes the frame of the last timed step — the same arrays from two runs with the same arguments, and the frame a
+    context of its own renders through the same passes (first pass, warm-up and timed steps of 8 passes, each tone-mapped)."""
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 3, 1
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--config", "A",
+               "--dump-outputs", str(out)]
+        proc = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        res = json.loads([l for l in proc.stdout.splitlines() if l.startswith("{")][-1])
+        assert res["steps"] == steps and res["timing"]["repeats"] == 1 and res["timing"]["passes_timed"] == steps * 8
+        assert res["value"] > 0 and res["ms_per_step"] > 0 and res["unit"] == "Mrays/s" and res["higher_is_better"] is True
+        assert res["dtype"] == "f32" and res["metric"]
+        assert not {"roofline", "end_to_end", "spp_per_s", "hosts_default_packaging", "other_shard_mode", "cpu_baseline"} & set(res)
+        dumps.append({name: np.load(out / f"{name}.npy") for name in ("accum", "image")})
+    for name in ("accum", "image"):
+        assert dumps[0][name].dtype == np.float32 and np.array_equal(dumps[0][name], dumps[1][name]), name
+
+    preset = scenes.CONFIGS["A"]
+    world = preset["build"]()
+    ctx = Context(0)
+    ctx.upload_scene(flatten(world))
+    ctx.upload_camera(camera_struct(world.camera))
+    ctx.set_config(RenderConfig(tracing=Tracing(preset["max_depth"], 8)).struct())
+    ctx.render(1)
+    for _ in range(warmup + steps):
+        ctx.render(8)
+        ctx.tonemap()
+    accum, image = ctx.read_accum(), ctx.read_rgba8()
+    ctx.close()
+    assert dumps[0]["accum"].shape == accum.shape and dumps[0]["image"].shape == image.shape[:2] + (3,)
+    assert np.array_equal(dumps[0]["accum"][..., 3], accum[..., 3]), "finished-path counts differ from the frame of the same passes"
+    assert np.allclose(dumps[0]["accum"], accum, rtol=1e-5, atol=1e-6), "accumulators differ from the frame of the same passes"
+    assert (np.abs(dumps[0]["image"] - image[..., :3]) <= 1).all(), "tone-mapped frame differs from the frame of the same passes"
+
+
 @pytest.mark.parametrize("overlap", [1, 0])
 def test_sharded_frame_streams_with_in_process_collective(built, overlap):
     """ShardedFrame's stream choreography (export on the render stream, gather + one-launch untile on the comm stream,

@@ -145,7 +145,7 @@ def test_bench_two_ranks_on_one_gpu(built, mode):
     (--verify-gather: samples against the sum of the two one-GPU frames on the ranks' seeds, tiles against the unsharded frame) for the
     one-stream packaging, the hosts' default packaging (two streams per rank) and the other shard mode."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1", "--min-seconds", "0", "--config", "A",
-           "--rehearse-on-one-gpu", "--no-cpu-baseline", "--verify-gather", "--shard-mode", mode]
+           "--rehearse-on-one-gpu", "--no-cpu-baseline", "--verify-gather", "--shard-mode", mode, "--full"]
     proc = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stdout[-1000:] + proc.stderr[-3000:]
     res = json.loads([l for l in proc.stdout.splitlines() if l.startswith("{")][-1])

@@ -3,5 +3,5 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for lib in $R/build/ab/libhiprz_*.so; do
   name=$(basename $lib .so)
-  HIPRZ_LIB=$lib python3 $R/bench.py --steps 10 --no-cpu-baseline "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', round(d['value'],1), 'Mrays/s', round(d['roofline']['avg_launch_us'],1), 'us')"
+  HIPRZ_LIB=$lib python3 $R/bench.py --full --steps 10 --no-cpu-baseline "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', round(d['value'],1), 'Mrays/s', round(d['roofline']['avg_launch_us'],1), 'us')"
 done

@@ -5,7 +5,7 @@ OUT=$R/$1
 shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o kp -- python3 $R/bench.py --no-cpu-baseline --streams 1 --steps 10 --warmup 2 --repeats 1 --min-seconds 0 "$@" > $OUT/bench.json 2> $OUT/err.log < /dev/null
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o kp -- python3 $R/bench.py --full --no-cpu-baseline --streams 1 --steps 10 --warmup 2 --repeats 1 --min-seconds 0 "$@" > $OUT/bench.json 2> $OUT/err.log < /dev/null
 F=$(find $OUT -name "*kernel_stats.csv" | head -1)
 if [ -z "$F" ]; then echo "no kernel stats written"; tail -5 $OUT/err.log; exit 1; fi
 python3 -c '

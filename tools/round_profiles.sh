@@ -17,6 +17,6 @@ for c in ${@:-B C D E}; do
   cp $R/gpurun_out/prof_$c/traffic.json $OUT/traffic_$c.json; cp $R/gpurun_out/prof_$c/traffic.json $R/profiles/traffic_$c.json
   python3 $R/tools/kstats.py $OUT/kernel_stats_$c.csv 6
   echo "progress: $c kernel stats + HBM counters done"
-  (cd $R && timeout -k 10 400 python3 bench.py --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err) || { tail -5 $OUT/bench_$c.err; exit 1; }
+  (cd $R && timeout -k 10 400 python3 bench.py --full --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err) || { tail -5 $OUT/bench_$c.err; exit 1; }
   python3 -c "import json; d=json.load(open('$OUT/bench_$c.json')); r=d['roofline']; print('$c', round(d['value'],1), 'Mrays/s', round(d['ms_per_step'],3), 'ms/step', r['kernel'].split(' ')[0], round(r['avg_launch_us'],1), 'us frac', round(r['frac'],3), 'valu_busy', r.get('valu_busy'), 'lanes', r.get('lanes_active'), 'traffic MB', (r.get('traffic') or 0)/1e6)"
 done

@@ -5,7 +5,7 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cfg=$1; shift
 run() {
-  timeout -k 10 200 python3 $R/bench.py --config $cfg --steps 6 --warmup 1 --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
+  timeout -k 10 200 python3 $R/bench.py --full --config $cfg --steps 6 --warmup 1 --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
 import sys, json, os
 d = json.loads(sys.stdin.read()); r = d['roofline']
 print('$cfg', 'K', os.environ.get('HIPRZ_WALK_K', '-'), 'L', os.environ.get('HIPRZ_WALK_L', '-'), 'waves', os.environ.get('HIPRZ_TRACE_WAVES', '-'), round(d['value'], 1), 'Mrays/s', r['kernel'].split(' ')[0], round(r['avg_launch_us'], 1), 'us')" || exit 1
