@@ -314,7 +314,7 @@ void release_frame(hiprz_frame_state* c) {
     c->st0.release(), c->st1.release(), c->st2.release(), c->accum.release(), c->depth.release(), c->rgba8.release();
     c->hit0.release(), c->hit1.release();
     c->nee.release(), c->prev_accum.release(), c->prev_depth.release();
-    c->unit_cost.release(), c->launch_order.release(), c->order_keys.release();
+    c->unit_cost.release(), c->launch_order.release(), c->order_keys.release(), c->seg_ctl.release();
     c->order_sort.keys_out.release(), c->order_sort.vals_a.release(), c->order_sort.vals_b.release(), c->order_sort.counts.release(), c->order_sort.row_total.release();
     c->sort_keys.release(), c->sort_perm.release();
     for (auto& t : c->sort_temp) t.keys_out.release(), t.vals_a.release(), t.vals_b.release(), t.counts.release(), t.row_total.release();
@@ -488,6 +488,11 @@ int allocate_frame(hiprz_ctx* c) {
             if (orc != HIPRZ_OK) return orc;
         }
         c->order_units = 0u, c->batches_since_order = 0u;
+    }
+    {   // the segmented batch kernel's control words + one word per unit of the (swizzle-padded) grid
+        const size_t words = hiprz::kSegFlags + ((size_t(c->n_local_tiles) + 7u) / 8u) * 8u;
+        RZ_HIP(c, c->seg_ctl.resize(words));
+        RZ_HIP(c, hipMemsetAsync(c->seg_ctl.ptr, 0, c->seg_ctl.count * sizeof(uint32_t), c->stream));
     }
     if (n) {
         RZ_HIP(c, hipMemsetAsync(c->accum.ptr, 0, n * sizeof(float4), c->stream));
@@ -1196,6 +1201,7 @@ int hiprz_create(hiprz_ctx** out, int device_id) {
     if (const char* w = std::getenv("HIPRZ_DEFER_SHADOWS")) c->defer_shadow_rays = std::atoi(w) != 0;
     if (const char* w = std::getenv("HIPRZ_HEAVY_FIRST")) c->heavy_first = std::atoi(w) != 0;
     if (const char* w = std::getenv("HIPRZ_BATCH_WAVES")) c->batch_waves = std::atoi(w);
+    if (const char* w = std::getenv("HIPRZ_BATCH_SEGMENTS")) c->batch_segments = std::max(0, std::atoi(w));
     if (const char* w = std::getenv("HIPRZ_NOLIGHT_KERNELS")) c->nolight_kernels = std::atoi(w) != 0;
     if (const char* w = std::getenv("HIPRZ_SORT_BITS")) c->sort_bits = std::min(24, std::max(0, std::atoi(w)));
     if (const char* w = std::getenv("HIPRZ_SHADOW_PACKET")) c->shadow_packet = std::atoi(w);
@@ -1203,6 +1209,7 @@ int hiprz_create(hiprz_ctx** out, int device_id) {
     if (const char* w = std::getenv("HIPRZ_SHADOW_SORT")) c->shadow_sort = std::atoi(w) != 0;
     if (const char* w = std::getenv("HIPRZ_WAVE_RESIDENT_MAX")) c->wave_resident_max = uint32_t(std::max(0, std::atoi(w)));
     c->device = device_id;
+    c->n_cus = uint32_t(std::max(1, prop.multiProcessorCount));
     c->parked.resize(1);  // one camera; its state lives in the context itself
     e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->peer_done, hipEventDisableTiming);

@@ -145,6 +145,9 @@ struct hiprz_frame_state {
     SortTemp order_sort;
     uint32_t order_units = 0;           // how many units launch_order permutes (0: none yet)
     uint32_t batches_since_order = 0;   // resident batches since the order was last derived
+    // the resident kernel in pass segments (rz_batch_seg_kernel): its queue, workgroup count and epoch base, then one published-segment
+    // word per unit; zeroed with the frame, never again from the host
+    hiprz::DeviceArray<uint32_t> seg_ctl;
     // HIPRZ_COMPAT_REPROJECTION: the frame a restart replaces (accumulator, first-hit depth, the camera it was rendered from)
     hiprz::DeviceArray<float4> prev_accum;
     hiprz::DeviceArray<float> prev_depth;
@@ -235,6 +238,11 @@ struct hiprz_ctx : hiprz_frame_state {
     uint32_t graph_captures = 0;  // how often a batch was captured + instantiated (hiprz_graph_captures)
     uint32_t n_textures = 0;  // of the uploaded scene
     int batch_waves = 0;  // HIPRZ_BATCH_WAVES=4: never the 5-wave build of the plain batch kernel
+    int batch_segments = 0;  // HIPRZ_BATCH_SEGMENTS=S >= 1: the resident batch kernel cuts every tile's passes into S segments (1: the unsegmented kernel); 0 = by grid size
+    uint32_t n_cus = 0;      // compute units of the device (the segmented kernel's grid is what they hold at once)
+    const void* seg_occ_kernel = nullptr;  // workgroups per CU of the last segmented instantiation launched, at seg_occ_lds bytes of LDS
+    size_t seg_occ_lds = 0;
+    int seg_occ_blocks = 0;
     int nolight_kernels = 1;  // scenes without lights use the instantiations without next-event estimation (HIPRZ_NOLIGHT_KERNELS=0: the general ones)
     bool flat_world = false;  // the uploaded world tree is one leaf of at most 8 instances: the binned walk tests their boxes up front (MODE 4)
     int sort_bits = 0;    // most significant key bits the radix sorts look at; 0 = by frame size (HIPRZ_SORT_BITS)
@@ -319,6 +327,18 @@ void launch_trace(hiprz_ctx* c, const DFrame& f, bool first, bool counted);   //
 void launch_shade(hiprz_ctx* c, const DFrame& f, bool first, bool counted);   // split pipeline: shading (+ deferred shadow rays and their sorts)
 void launch_fused(hiprz_ctx* c, const DFrame& f, bool first, bool counted);   // fused pipeline: one kernel per pass
 void launch_batch(hiprz_ctx* c, const DFrame& f, uint32_t n_passes, bool counted, hipEvent_t before, hipEvent_t after);  // resident pipeline
+// the resident batch kernel's instantiation and launch geometry as launch_batch chose them
+struct BatchVariant {
+    int mode;             // 1 LDS stack, 2 workgroup-binned, 4 binned with the one-leaf world
+    bool lds_scene;       // the hot blob is staged into LDS
+    int shading;          // 1 general, RZ_SHADOW_NONE, RZ_SHADOW_PLAIN
+    bool five;            // the 5-wave build (plain shading only)
+    uint32_t units;       // tiles of the (swizzle-padded) grid
+    size_t lds;           // dynamic LDS per workgroup
+    uint32_t park_offset; // where the parked state starts behind the scene blob
+};
+// hiprz_launch_batch_seg.hip: the batch with every tile's passes cut into `segments` self-scheduled segments (rz_batch_seg_kernel)
+void launch_batch_segmented(hiprz_ctx* c, const DFrame& f, uint32_t n_passes, uint32_t segments, bool counted, const BatchVariant& v);
 void launch_sort(hiprz_ctx* c, bool beside = false);  // keys of the next rays -> the permutation the next trace kernel follows;
                                                       // beside: on the auxiliary stream, joined by join_sort()
 void join_sort(hiprz_ctx* c);

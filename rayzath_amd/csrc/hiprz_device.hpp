@@ -172,6 +172,9 @@ struct DFrame {
     const uint32_t* launch_order;
     uint32_t* unit_cost;
 };
+// the segmented resident kernel's control block (rz_batch_seg_kernel): queue, workgroups done, epoch base, spare; the units' words follow
+constexpr uint32_t kSegFlags = 4u;
+constexpr uint32_t kSegWaitLimit = 1u << 22;  // polls of a segment's predecessor flag (a segment lasts ~100 us, a poll ~1 us)
 
 struct v3 {
     float x, y, z;

@@ -44,8 +44,37 @@ RZ_DEV uint32_t stage_scene(DScene& s, unsigned char* lds) {
     return 0u;
 }
 
+// State handed from one workgroup to another INSIDE a launch (rz_batch_seg_kernel) crosses the XCDs' private L2s: it is stored
+// write-through and loaded past this CU's L1 (agent-scope relaxed atomics of 8 bytes: sc1 stores and loads), so neither side needs a
+// release or acquire fence around the hand-over flag.
+RZ_DEV uint64_t ld_agent(const void* p) { return __hip_atomic_load(static_cast<uint64_t*>(const_cast<void*>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+RZ_DEV void st_agent(void* p, uint64_t v) { __hip_atomic_store(static_cast<uint64_t*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+RZ_DEV float2 as_float2(uint64_t v) { return make_float2(__uint_as_float(uint32_t(v)), __uint_as_float(uint32_t(v >> 32))); }
+RZ_DEV uint64_t as_u64(float a, float b) { return uint64_t(__float_as_uint(a)) | (uint64_t(__float_as_uint(b)) << 32); }
+template <bool SC1, typename T>
+RZ_DEV T load_state(const T* p) {
+    if constexpr (!SC1) {
+        return *p;
+    } else if constexpr (sizeof(T) == 8) {
+        return as_float2(ld_agent(p));
+    } else {
+        const float2 lo = as_float2(ld_agent(p)), hi = as_float2(ld_agent(reinterpret_cast<const float2*>(p) + 1));
+        return make_float4(lo.x, lo.y, hi.x, hi.y);
+    }
+}
+template <bool SC1>
+RZ_DEV void store_state(float4* p, float4 v) {
+    if constexpr (SC1) st_agent(p, as_u64(v.x, v.y)), st_agent(reinterpret_cast<float2*>(p) + 1, as_u64(v.z, v.w));
+    else *p = v;
+}
+template <bool SC1>
+RZ_DEV void store_state(float2* p, float2 v) {
+    if constexpr (SC1) st_agent(p, as_u64(v.x, v.y));
+    else *p = v;
+}
+
 // the segment's ray: generateSimpleRay on the first pass, CameraContext::getRay afterwards
-template <bool FIRST>
+template <bool FIRST, bool SC1 = false>
 RZ_DEV void load_path(const DFrame& f, const DCamera& cam, const PixelId& p, PathState& ps) {
     ps.color = splat(1.0f);
     ps.material = HIPRZ_MATERIAL_WORLD, ps.depth = 0u;
@@ -54,8 +83,8 @@ RZ_DEV void load_path(const DFrame& f, const DCamera& cam, const PixelId& p, Pat
     if constexpr (FIRST) {
         generate_simple_ray(cam, ps.ray, p.x, p.y);
     } else {
-        const float4 s0 = f.st0[p.local], s1 = f.st1[p.local];
-        const float2 s2 = f.st2[p.local];
+        const float4 s0 = load_state<SC1>(f.st0 + p.local), s1 = load_state<SC1>(f.st1 + p.local);
+        const float2 s2 = load_state<SC1>(f.st2 + p.local);
         const uint32_t bits = __float_as_uint(s2.y);
         ps.ray.o = V3(s0.x, s0.y, s0.z);
         ps.ray.d = normalized(V3(s0.w, s1.x, s1.y));  // SceneRay ctor normalises (cpu_render_utils.hpp:41-46)
@@ -304,33 +333,24 @@ __global__ void __launch_bounds__(256, RZ_MIN_WAVES) rz_pass_kernel(const DScene
 // pixel is written on the way out.  Per pixel the arithmetic is that of n_passes launches of the fused kernel: the
 // direction is re-normalised at the start of every segment as load_path does after reading it back, and the
 // accumulator grows by the same sequence of additions.
-// WAVES = waves per SIMD the register budget is cut for.  With 29 KB of LDS per workgroup (a Cornell-sized scene) five workgroups
-// fit a CU, and when the grid oversubscribes the chip the 5-wave build of the plain instantiation wins although it spills more
-// (96 VGPRs, 148 B of scratch: whole 1080p frame 2.15 -> 2.04 ms per step); a grid that fits the chip at once — an eighth of the
-// frame on each of 8 GPUs — runs faster on the 4-wave build (0.326 against 0.350 ms), so launch_batch picks by grid size.
-template <bool COUNT, int MODE, bool LDS_SCENE, int SHADING, int WAVES = RZ_MIN_WAVES>  // SHADING: 1 general, RZ_SHADOW_NONE (no lights), RZ_SHADOW_PLAIN (no lights, no maps)
-__global__ void __launch_bounds__(256, WAVES) rz_batch_kernel(const DScene scene_in, const DCamera cam, const DConfig cfg, const DFrame f,
-                                                                      uint32_t n_passes, uint32_t park_offset) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rz_lds[];
-    const unsigned long long t_start = __builtin_readcyclecounter();
-    const uint32_t unit = (f.launch_order && !f.xcd_swizzle) ? f.launch_order[blockIdx.x] : blockIdx.x;  // heaviest tiles first (DFrame::launch_order)
-    const PixelId p = pixel_of_thread(f, cam, unit, threadIdx.x);
-    if (!p.tile_inside) return;  // (the whole workgroup: the padding of the swizzled grid)
-    DScene s = scene_in;
-    unsigned char* workspace = rz_lds + stage_scene<LDS_SCENE>(s, rz_lds);
+//
+// One tile through the passes [pass0, pass0 + n_passes) of a render batch: state and accumulator are read back from HBM as
+// load_path does, and written there again at the end; the tone-mapped pixel only when `tonemap_out` (the batch's last pass).
+// `workspace` holds the walk's LDS, `park` (+ threadIdx.x) the thread's 8 parked words.  SC1: state and accumulator are handed to or
+// from another workgroup of the launch (load_state / store_state).
+template <bool COUNT, int MODE, int SHADING, bool SC1 = false>
+RZ_DEV void batch_tile(const DScene& s, const DCamera& cam, const DConfig& cfg, const DFrame& f, unsigned char* workspace, uint32_t* park,
+                       const PixelId& p, uint32_t pass0, uint32_t n_passes, bool tonemap_out, Counters& cnt) {
     uint32_t* lds_column = stack_column<MODE>(workspace);
-    Counters cnt;
     PathState ps;
-    load_path<false>(f, cam, p, ps);
+    load_path<false, SC1>(f, cam, p, ps);
     // the accumulator lives in LDS for the whole batch (touched once per pass); colour / material / depth join it
     // there while the binned walk runs
-    uint32_t* park = reinterpret_cast<uint32_t*>(workspace + park_offset) + threadIdx.x;
     {
-        const float4 acc = p.active ? f.accum[p.local] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const float4 acc = p.active ? load_state<SC1>(f.accum + p.local) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         park[4 * 256] = __float_as_uint(acc.x), park[5 * 256] = __float_as_uint(acc.y);
         park[6 * 256] = __float_as_uint(acc.z), park[7 * 256] = __float_as_uint(acc.w);
     }
-    const uint32_t pass0 = *f.pass;
     for (uint32_t i = 0; i < n_passes; ++i) {
         if (i != 0u && p.active) {  // what load_path does with the state the previous pass stored
             ps.ray.d = normalized(ps.ray.d);
@@ -359,20 +379,109 @@ __global__ void __launch_bounds__(256, WAVES) rz_batch_kernel(const DScene scene
             park[7 * 256] = __float_as_uint(__uint_as_float(park[7 * 256]) + float(!path_continues));
         }
     }
-    if (p.active) {
+    if (p.active) {  // the direction as it stands: the next batch's load_path normalises it, as the loop above does at i != 0
         const float4 acc = make_float4(__uint_as_float(park[4 * 256]), __uint_as_float(park[5 * 256]), __uint_as_float(park[6 * 256]),
                                        __uint_as_float(park[7 * 256]));
-        f.accum[p.local] = acc;
-        f.st0[p.local] = make_float4(ps.ray.o.x, ps.ray.o.y, ps.ray.o.z, ps.ray.d.x);
-        f.st1[p.local] = make_float4(ps.ray.d.y, ps.ray.d.z, ps.color.r, ps.color.g);
-        f.st2[p.local] = make_float2(ps.color.b, __uint_as_float((ps.material & 0xFFFFu) | (ps.depth << 16)));
-        f.rgba8[p.local] = tonemap(col4{acc.x, acc.y, acc.z, acc.w}, cam.aperture, cam.exposure_time);
+        store_state<SC1>(f.accum + p.local, acc);
+        store_state<SC1>(f.st0 + p.local, make_float4(ps.ray.o.x, ps.ray.o.y, ps.ray.o.z, ps.ray.d.x));
+        store_state<SC1>(f.st1 + p.local, make_float4(ps.ray.d.y, ps.ray.d.z, ps.color.r, ps.color.g));
+        store_state<SC1>(f.st2 + p.local, make_float2(ps.color.b, __uint_as_float((ps.material & 0xFFFFu) | (ps.depth << 16))));
+        if (tonemap_out) f.rgba8[p.local] = tonemap(col4{acc.x, acc.y, acc.z, acc.w}, cam.aperture, cam.exposure_time);
     }
+}
+
+// WAVES = waves per SIMD the register budget is cut for.  With 29 KB of LDS per workgroup (a Cornell-sized scene) five workgroups
+// fit a CU, and when the grid oversubscribes the chip the 5-wave build of the plain instantiation wins although it spills more
+// (96 VGPRs, 148 B of scratch: whole 1080p frame 2.15 -> 2.04 ms per step); a grid that fits the chip at once — an eighth of the
+// frame on each of 8 GPUs — runs faster on the 4-wave build (0.326 against 0.350 ms), so launch_batch picks by grid size.
+template <bool COUNT, int MODE, bool LDS_SCENE, int SHADING, int WAVES = RZ_MIN_WAVES>  // SHADING: 1 general, RZ_SHADOW_NONE (no lights), RZ_SHADOW_PLAIN (no lights, no maps)
+__global__ void __launch_bounds__(256, WAVES) rz_batch_kernel(const DScene scene_in, const DCamera cam, const DConfig cfg, const DFrame f,
+                                                                      uint32_t n_passes, uint32_t park_offset) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rz_lds[];
+    const unsigned long long t_start = __builtin_readcyclecounter();
+    const uint32_t unit = (f.launch_order && !f.xcd_swizzle) ? f.launch_order[blockIdx.x] : blockIdx.x;  // heaviest tiles first (DFrame::launch_order)
+    const PixelId p = pixel_of_thread(f, cam, unit, threadIdx.x);
+    if (!p.tile_inside) return;  // (the whole workgroup: the padding of the swizzled grid)
+    DScene s = scene_in;
+    unsigned char* workspace = rz_lds + stage_scene<LDS_SCENE>(s, rz_lds);
+    Counters cnt;
+    uint32_t* park = reinterpret_cast<uint32_t*>(workspace + park_offset) + threadIdx.x;
+    batch_tile<COUNT, MODE, SHADING>(s, cam, cfg, f, workspace, park, p, *f.pass, n_passes, true, cnt);
     if (f.unit_cost && threadIdx.x == 0u) {  // what this unit's batch cost: the next launches start the expensive units first
         const unsigned long long dt = (__builtin_readcyclecounter() - t_start) >> 4;
         f.unit_cost[unit] = dt < 0x00FFFFFFull ? uint32_t(dt) : 0x00FFFFFFu;
     }
     flush_counters<COUNT>(f, p.active ? n_passes : 0u, cnt);
+}
+
+// ---- resident pipeline in pass segments: a shorter end of the launch ----
+// A work unit of rz_batch_kernel is a tile carried through all the passes of the batch; 8 100 tiles of a 1080p frame are 6.3 rounds of
+// the chip's 1 280 workgroup slots, and the slots that finish their last tile early stay idle until the slowest one is done.  Here the
+// passes of a tile are cut into `segments` runs, [k n / S, (k + 1) n / S), and the item (tile, k) is the work unit: the launch ends on
+// units S times shorter.  The grid is what the chip holds at once; its workgroups stage the scene once and take items from a queue in
+// the order segment 0 of every tile (heaviest first), then segment 1, ... — an item's predecessor (same tile, k - 1) has always been
+// taken before it by a workgroup that is running, so waiting for it cannot deadlock, resident grid or not.  Between the segments of a
+// tile its path state and accumulator go through HBM as between two render calls (batch_tile: the same arithmetic, the same frames).
+// seg: [0] the queue, [1] workgroups done, [2] the launch's epoch base, [3] unused, [4 + unit] the unit's last published segment.
+// The last workgroup to finish resets the queue and advances the base by `segments`, so no word needs a reset from the host: in a launch
+// of base B, segment k of a unit publishes B + k + 1 and segment k + 1 waits for exactly that; every value older launches left is < B + 1.
+template <bool COUNT, int MODE, bool LDS_SCENE, int SHADING, int WAVES = RZ_MIN_WAVES>
+__global__ void __launch_bounds__(256, WAVES) rz_batch_seg_kernel(const DScene scene_in, const DCamera cam, const DConfig cfg, const DFrame f,
+                                                                          uint32_t n_passes, uint32_t park_offset, uint32_t segments, uint32_t n_units,
+                                                                          uint32_t* seg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rz_lds[];
+    DScene s = scene_in;
+    unsigned char* workspace = rz_lds + stage_scene<LDS_SCENE>(s, rz_lds);
+    uint32_t* park = reinterpret_cast<uint32_t*>(workspace + park_offset) + threadIdx.x;
+    uint32_t* item_slot = reinterpret_cast<uint32_t*>(workspace + park_offset + 8u * 1024u);  // (16 B behind the park)
+    const uint32_t n_items = segments * n_units, pass_base = *f.pass;
+    uint32_t base = 0u;
+    if (threadIdx.x == 0u) base = __hip_atomic_load(&seg[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        if (threadIdx.x == 0u) item_slot[0] = __hip_atomic_fetch_add(&seg[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const uint32_t item = item_slot[0];
+        if (item >= n_items) break;
+        const uint32_t k = item / n_units, j = item - k * n_units;
+        const uint32_t unit = (f.launch_order && !f.xcd_swizzle) ? f.launch_order[j] : j;
+        const PixelId p = pixel_of_thread(f, cam, unit, threadIdx.x);
+        if (p.tile_inside) {  // (the whole workgroup: the padding of the swizzled grid has no segments to wait for)
+            if (k != 0u) {  // the previous segment's state and accumulator: written through to memory before its flag, read past the caches
+                if (threadIdx.x == 0u) {
+                    // a guard like the walks', always on here (a poll costs nothing beside the wait): a lost flag gives wrong pixels after
+                    // a few seconds, never a hung chip
+                    for (uint32_t guard = 0u; __hip_atomic_load(&seg[kSegFlags + unit], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != base + k;) {
+                        __builtin_amdgcn_s_sleep(2);
+                        if (++guard > kSegWaitLimit) break;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // (no instruction: keeps the loads below the poll)
+                }
+                __syncthreads();
+            }
+            const unsigned long long t_start = __builtin_readcyclecounter();
+            const uint32_t first = k * n_passes / segments, end = (k + 1u) * n_passes / segments;
+            Counters cnt;
+            batch_tile<COUNT, MODE, SHADING, true>(s, cam, cfg, f, workspace, park, p, pass_base + first, end - first, k + 1u == segments, cnt);
+            if (f.unit_cost && threadIdx.x == 0u) {  // the tile's cost is the sum over its segments (launch_order keeps its meaning)
+                const uint32_t before = k != 0u ? __hip_atomic_load(&f.unit_cost[unit], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+                const unsigned long long dt = ((__builtin_readcyclecounter() - t_start) >> 4) + before;
+                __hip_atomic_store(&f.unit_cost[unit], dt < 0x00FFFFFFull ? uint32_t(dt) : 0x00FFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            flush_counters<COUNT>(f, p.active ? end - first : 0u, cnt);
+            if (k + 1u != segments) {  // publish: every wave's write-through stores have reached memory, then one lane's flag
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                if (threadIdx.x == 0u) __hip_atomic_store(&seg[kSegFlags + unit], base + k + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __syncthreads();  // (item_slot and the LDS workspace are free again)
+    }
+    if (threadIdx.x == 0u && __hip_atomic_fetch_add(&seg[1], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) {
+        // the last workgroup: every other one has drawn its last item; the next launch (stream order) starts from a fresh queue
+        __hip_atomic_store(&seg[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&seg[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&seg[2], base + segments, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 // ---- resident pipeline for scenes that are not staged in LDS (no lights): one WAVE takes its 64 pixels through all the passes ----

@@ -1,10 +1,14 @@
 // hiprz_launch_batch.hip — the fused pass kernel (one kernel per pass; the resident pipeline's renderFirstPass) and the
 // resident batch kernel (ONE launch takes every owned tile through all the cumulative passes of a render call).
+#include <algorithm>
+
 #include "hiprz_ctx.hpp"
 #include "hiprz_kernels.hpp"
 
 namespace hiprz {
 namespace {
+
+constexpr uint32_t kBatchSegments = 2u;  // pass segments per tile where the grid oversubscribes the chip (B: S = 2 +2.0 %, 3 +0.6 %, 4 -0.5 %, 8 -7.6 %)
 
 template <bool FIRST, bool COUNT>
 void launch_fused_t(hiprz_ctx* c, const DFrame& f) {
@@ -53,6 +57,16 @@ void launch_batch_t(hiprz_ctx* c, const DFrame& f, uint32_t n) {
     const bool plain = dark && c->n_textures == 0u;
     // 5 workgroups per CU must fit LDS, and the grid must be more than two full loads of the chip (256 CUs x 5)
     const bool five = lds * 5u <= 160u * 1024u && grid.x > 2u * 5u * 256u && c->batch_waves != 4;
+    // Pass segments (rz_batch_seg_kernel): where the grid oversubscribes the chip, the launch otherwise ends on whole tiles' chains of
+    // passes; measured on config B.  A grid that fits the chip in one round has no such tail.  HIPRZ_BATCH_SEGMENTS
+    // forces S everywhere (1: the unsegmented kernel).
+    const uint32_t segments = std::min(n, c->batch_segments > 0 ? uint32_t(c->batch_segments) : (plain && five ? kBatchSegments : 1u));
+    if (segments > 1u) {
+        const int m = g.mode == 2 ? (g.lds_scene && c->flat_world ? 4 : 2) : 1;
+        const int shading = plain ? RZ_SHADOW_PLAIN : dark ? RZ_SHADOW_NONE : 1;
+        launch_batch_segmented(c, f, n, segments, COUNT, BatchVariant{m, g.lds_scene, shading, plain && five, grid.x, lds, park_offset});
+        return;
+    }
 #define RZ_BATCH(M, L)                                                                                                                     \
     do {                                                                                                                                   \
         if (plain && five) RZ_LAUNCH((rz_batch_kernel<COUNT, M, L, RZ_SHADOW_PLAIN, 5>), grid, block, lds, c->stream, c->dscene, c->dcamera, cfg, f, n, park_offset); \
