@@ -511,6 +511,30 @@ typedef struct hiprz_raycast {
 int hiprz_ray_cast(hiprz_ctx* ctx, uint32_t x, uint32_t y, hiprz_raycast* out);
 int hiprz_pick(hiprz_ctx* ctx, uint32_t x, uint32_t y, int32_t* instance_out, int32_t* material_out); /* instance + material of hiprz_ray_cast */
 
+/* --- pipelined frame delivery (EngineCore::CopyRenderToHost with sync = false, cuda_engine_core.cu:115-120, 129-242) ---
+ * hiprz_present tone-maps the selected camera's frame (as hiprz_tonemap), assembles its RGBA8 image, depth and the ray cast through
+ * (ray_cast_x, ray_cast_y) on the device into one of the camera's two frame slots, and lets the context's copy stream move that slot into
+ * pinned host memory.  It only enqueues: the next hiprz_render can follow at once, and frame N travels to the host while N+1 renders.
+ * hiprz_read_frame waits for that copy alone.  `sequence` 0 = the newest presented frame; only the newest two sequences of the selected
+ * camera can be read (any other: HIPRZ_ERR_STATE).
+ * The view's pointers stay valid until the second hiprz_present after it on that camera, or until the camera is resized
+ * (hiprz_upload_camera with another width or height, which also restarts the sequence at 1), dropped (hiprz_set_camera_count) or the
+ * context destroyed.  A copy that failed on the device surfaces as HIPRZ_ERR_DEVICE from the next hiprz_read_frame / hiprz_present.
+ * The frame equals what hiprz_read_rgba8, hiprz_read_depth, hiprz_pass_count, hiprz_ray_count and hiprz_ray_cast answer at the present. */
+typedef struct hiprz_frame {
+    const uint8_t* rgba8; /* W*H*4, row-major; pinned host memory owned by the context */
+    const float* depth;   /* W*H, row-major (what hiprz_read_depth returns)            */
+    uint32_t width, height;
+    uint32_t passes;      /* hiprz_pass_count at the present                           */
+    uint32_t sequence;    /* 1, 2, ... per camera                                      */
+    uint64_t ray_count;   /* hiprz_ray_count at the present                            */
+    hiprz_raycast hit;    /* == hiprz_ray_cast(x, y) at the present                    */
+} hiprz_frame;
+int hiprz_present(hiprz_ctx* ctx, uint32_t ray_cast_x, uint32_t ray_cast_y); /* enqueue only: never waits for the GPU */
+int hiprz_read_frame(hiprz_ctx* ctx, uint32_t sequence, hiprz_frame* out);   /* 0 = newest presented; waits for its copy */
+/* sizeof(hiprz_frame) and the offsets of ray_count and hit as this library was compiled (out[3]) */
+void hiprz_frame_layout(uint32_t out[3]);
+
 /* Device self-test of the kernels' exact-arithmetic shortcuts (shared-reciprocal division must
  * equal the correctly rounded quotient): runs 262144 * cases_per_thread random cases. */
 int hiprz_selftest(hiprz_ctx* ctx, uint32_t cases_per_thread, uint32_t seed, uint64_t* mismatches, uint64_t* tested);

@@ -99,6 +99,11 @@ class RayCast(C.Structure):  # hiprz_raycast
     _fields_ = [("instance", C.c_int32), ("material_slot", C.c_int32), ("material", C.c_int32), ("triangle", C.c_uint32)]
 
 
+class Frame(C.Structure):  # hiprz_frame (hiprz_present / hiprz_read_frame)
+    _fields_ = [("rgba8", C.POINTER(C.c_uint8)), ("depth", C.POINTER(C.c_float)), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("passes", C.c_uint32), ("sequence", C.c_uint32), ("ray_count", C.c_uint64), ("hit", RayCast)]
+
+
 # name -> (restype, argtypes) of every entry point include/hiprz.h declares
 P = C.c_void_p
 U32, U64, SZ, I32 = C.c_uint32, C.c_uint64, C.c_size_t, C.c_int32
@@ -161,6 +166,9 @@ ENTRY_POINTS = {
     "hiprz_stream": (P, [P]),
     "hiprz_pick": (C.c_int, [P, U32, U32, C.POINTER(I32), C.POINTER(I32)]),
     "hiprz_ray_cast": (C.c_int, [P, U32, U32, C.POINTER(RayCast)]),
+    "hiprz_present": (C.c_int, [P, U32, U32]),
+    "hiprz_read_frame": (C.c_int, [P, U32, C.POINTER(Frame)]),
+    "hiprz_frame_layout": (None, [P]),
     "hiprz_selftest": (C.c_int, [P, U32, U32, C.POINTER(U64), C.POINTER(U64)]),
     "hiprz_selftest_sort": (C.c_int, [P, C.POINTER(U32), U32, C.c_int, U32, C.POINTER(U64), C.POINTER(C.c_double)]),
     "hiprz_timings": (C.c_int, [P, C.c_char_p, SZ]),

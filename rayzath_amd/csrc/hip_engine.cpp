@@ -2,7 +2,9 @@
 // C-ABI lives in hiprz_api.hip / hiprz_host.cpp.
 #include "hip_engine.hpp"
 
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <map>
 
@@ -364,17 +366,16 @@ void Engine::tree(uint32_t tree) {
     m_last_world = nullptr;  // takes effect at the next scene upload: force one
 }
 
-void Engine::readback(Camera& camera, const World& world) {
-    const size_t n = size_t(camera.width) * camera.height;
-    camera.image_buffer.resize(n * 4);
-    camera.depth_buffer.resize(n);
-    check(hiprz_read_rgba8(m_ctx, camera.image_buffer.data(), n * 4));
-    check(hiprz_read_depth(m_ctx, camera.depth_buffer.data(), n * sizeof(float)));
-    check(hiprz_ray_count(m_ctx, &camera.ray_count));
+void Engine::deliver(Camera& camera, const World& world, uint32_t sequence) {
+    hiprz_frame f{};
+    check(hiprz_read_frame(m_ctx, sequence, &f));
+    const size_t n = size_t(f.width) * f.height;
+    camera.image_buffer.assign(f.rgba8, f.rgba8 + n * 4);
+    camera.depth_buffer.assign(f.depth, f.depth + n);
+    camera.ray_count = f.ray_count;
     // Kernel::rayCast after every frame (cpu_engine_renderer.cpp:176; cuda_engine_core.cu:164-181): the instance and the instance's
-    // material slot the ray through the camera's ray-cast pixel meets at the first-hit depth
-    hiprz_raycast hit{};
-    check(hiprz_ray_cast(m_ctx, camera.ray_cast_pixel[0], camera.ray_cast_pixel[1], &hit));
+    // material slot the ray through the camera's ray-cast pixel meets at the first-hit depth (hiprz_present cast it on the device)
+    const hiprz_raycast hit = f.hit;
     camera.raycasted_instance.reset(), camera.raycasted_material.reset();
     if (hit.instance >= 0 && size_t(hit.instance) < world.instances.size()) {
         camera.raycasted_instance = world.instances[size_t(hit.instance)];
@@ -413,15 +414,28 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
         }
     }
     const std::vector<Camera*> cameras = enabledCameras(world);
-    if (m_pending_readback) {  // pipelined frames of the previous non-sync call
-        m_pending_readback = false;
-        for (size_t k = 0; k < m_camera_slots.size(); ++k)
-            for (Camera* cam : cameras)
-                if (cam == m_camera_slots[k]) {
-                    check(hiprz_select_camera(m_ctx, uint32_t(k)));
-                    readback(*cam, world);
-                }
-    }
+    // pipelined frames of the previous non-sync call: every camera still enabled gets its frame once this call's renders are enqueued
+    // (the first call after a (re)start has none, and leaves the buffers as they are)
+    std::vector<PendingFrame> pending;
+    pending.swap(m_pending_frames);
+    if (!m_pending_readback) pending.clear();
+    m_pending_readback = false;
+    pending.erase(std::remove_if(pending.begin(), pending.end(),
+                                 [&](const PendingFrame& p) {
+                                     return std::find(cameras.begin(), cameras.end(), p.camera) == cameras.end() ||
+                                            p.slot >= m_camera_slots.size() || m_camera_slots[p.slot] != p.camera;
+                                 }),
+                  pending.end());
+    auto deliver_pending = [&](size_t slot) {  // before what would free a camera's frame slots: hand out its frame now
+        for (auto it = pending.begin(); it != pending.end();)
+            if (slot == SIZE_MAX || it->slot == slot) {
+                check(hiprz_select_camera(m_ctx, uint32_t(it->slot)));
+                deliver(*it->camera, world, it->sequence);
+                it = pending.erase(it);
+            } else {
+                ++it;
+            }
+    };
     // re-mirror what changed; any change restarts accumulation (cpu_engine_renderer.cpp:108-112)
     bool moved_in_place = false;
     if (world.isMoved() && !world.isModified() && m_last_world == &world && world.instances.size() == m_uploaded_instances) {
@@ -481,7 +495,10 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
     bool slots_changed = m_camera_slots.size() != cameras.size();
     for (size_t k = 0; !slots_changed && k < cameras.size(); ++k) slots_changed = m_camera_slots[k] != cameras[k];
     if (slots_changed) {
-        check(hiprz_set_camera_count(m_ctx, uint32_t(std::max<size_t>(cameras.size(), 1))));
+        deliver_pending(SIZE_MAX);
+        const size_t n_slots = std::max<size_t>(cameras.size(), 1);
+        check(hiprz_set_camera_count(m_ctx, uint32_t(n_slots)));
+        m_presented.resize(n_slots, 0u), m_frame_sizes.resize(n_slots, {0u, 0u});
         m_camera_slots.assign(cameras.begin(), cameras.end());
         m_camera_records.assign(cameras.size(), hiprz_camera{});
         for (Camera* cam : cameras) cam->makeModified();
@@ -494,6 +511,10 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
             // an upload restarts accumulation (cpu_engine_renderer.cpp:108-112); a camera that only moved its ray-cast pixel
             // (Camera::rayCastPixel: MakeModified, not RequestUpdate) keeps accumulating in both reference engines
             if (slots_changed || std::memcmp(&rec, &m_camera_records[k], sizeof rec) != 0) {
+                if (m_frame_sizes[k] != std::make_pair(rec.width, rec.height)) {  // new frame slots, the sequence restarts
+                    deliver_pending(k);
+                    m_presented[k] = 0u, m_frame_sizes[k] = {rec.width, rec.height};
+                }
                 check(hiprz_upload_camera(m_ctx, &rec));
                 m_camera_records[k] = rec;
             }
@@ -501,12 +522,22 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
             cam.makeUnmodified();
         }
         check(hiprz_render(m_ctx, std::max(cfg.tracing.rpp, 1u)));
-        check(hiprz_tonemap(m_ctx));
-        if (sync) readback(cam, world);
+        // tone map, assemble and ray-cast the frame on the device, copy it to pinned memory on the context's copy stream: enqueued only
+        check(hiprz_present(m_ctx, cam.ray_cast_pixel[0], cam.ray_cast_pixel[1]));
+        const uint32_t sequence = ++m_presented[k];
+        if (sync) deliver(cam, world, sequence);
+        else m_pending_frames.push_back({k, &cam, sequence});
     }
-    // not sync: nothing has been waited for — the buffers are filled by the next call, and a device fault would surface at that
-    // call's first hip* return
-    if (!sync) m_pending_readback = true;
+    // not sync: nothing of this call's frames has been waited for — the buffers are filled by the next call, and a device fault would
+    // surface at that call's first hip* return.  The previous call's frames travelled to the host while these renders were enqueued.
+    if (!sync) {
+        for (const PendingFrame& p : pending) {
+            check(hiprz_select_camera(m_ctx, uint32_t(p.slot)));
+            deliver(*p.camera, world, p.sequence);
+        }
+        if (!pending.empty() && !cameras.empty()) check(hiprz_select_camera(m_ctx, uint32_t(cameras.size() - 1)));
+        m_pending_readback = true;
+    }
 }
 
 std::string Engine::timingsString() {

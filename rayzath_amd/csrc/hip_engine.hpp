@@ -248,7 +248,8 @@ public:
 
 private:
     void check(int rc);
-    void readback(Camera& camera, const World& world);
+    // camera `camera` gets frame `sequence` of the selected camera of the context (hiprz_read_frame: waits for that frame's copy only)
+    void deliver(Camera& camera, const World& world, uint32_t sequence);
     std::vector<Camera*> enabledCameras(World& world) const;
 
     hiprz_ctx* m_ctx = nullptr;
@@ -257,6 +258,14 @@ private:
     uint32_t m_mode = 0, m_tree = HIPRZ_TREE_AUTO;  // what mode() / tree() set (the hosts' default trees: per scene), for the context that replaces it
     std::mutex m_mutex;  // renderWorld is serialised (cpu_engine_core.cpp:15)
     bool m_pending_readback = false;
+    struct PendingFrame {  // a frame a non-sync call presented: the next call hands it out once its own renders are enqueued
+        size_t slot;
+        Camera* camera;
+        uint32_t sequence;
+    };
+    std::vector<PendingFrame> m_pending_frames;
+    std::vector<uint32_t> m_presented;                           // camera k of the context: sequence of its newest hiprz_present
+    std::vector<std::pair<uint32_t, uint32_t>> m_frame_sizes;   // ... and the size of its frame slots (an upload at another size restarts the sequence)
     std::unique_ptr<Exception> m_deferred;
     const World* m_last_world = nullptr;
     std::vector<const Camera*> m_camera_slots;  // camera k of the context mirrors this camera

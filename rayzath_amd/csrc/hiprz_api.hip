@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(256) rz_untile_state_kernel(const float4* st0,
 }
 
 // Kernel::rayCast (cpu_engine_kernel.cpp:102-111, 483-501): one thread.
-__global__ void rz_pick_kernel(const DScene s, const DCamera cam, uint32_t x, uint32_t y, float depth, int32_t* out4) {
+__device__ inline void pick_at(const DScene& s, const DCamera& cam, uint32_t x, uint32_t y, float depth, int32_t* out4) {
     Ray ray;
     generate_simple_ray(cam, ray, x, y);
     ray.near_ = depth * 0.99f;
@@ -128,6 +128,49 @@ __global__ void rz_pick_kernel(const DScene s, const DCamera cam, uint32_t x, ui
         out4[2] = slot < material_count ? s.inst_materials[material_base + slot] : -1;
         out4[3] = int32_t(__float_as_uint(s.tris[3 * hit.triangle + 1].w));  // hiprz_tri::source_index
     }
+}
+__global__ void rz_pick_kernel(const DScene s, const DCamera cam, uint32_t x, uint32_t y, float depth, int32_t* out4) {
+    pick_at(s, cam, x, y, depth, out4);
+}
+// hiprz_present: the same ray cast with the depth taken from the assembled row-major frame on the device (no host round trip).  `owned`: a
+// part of this context rendered pixel (x, y) — hiprz_ray_cast answers "nothing met" for pixels of shards rendered elsewhere.
+__global__ void rz_pick_slot_kernel(const DScene s, const DCamera cam, uint32_t x, uint32_t y, uint32_t owned, const float* depth, int32_t* out4) {
+    if (!owned) {
+        out4[0] = out4[1] = out4[2] = -1, out4[3] = 0;
+        return;
+    }
+    pick_at(s, cam, x, y, depth[size_t(y) * cam.width + x], out4);
+}
+
+// hiprz_present: tile-major rgba8 + depth -> the row-major frame slot, both images in one launch.  One workgroup per 32x8 tile of shard
+// rank0 + blockIdx.y of `world`; thread t moves pixel (t % 32, t / 32) of its tile, so that every 32 lanes store one row of the tile as 128
+// contiguous bytes per image (the reads gather 4 runs of 8 pixels: the in-tile order is ((x%32)/8)*64 + (y%8)*8 + x%8).
+// Gathered = false: the context's own tiles (blockIdx.y = 0).  Gathered = true: slice 0 is the head's own, slice r >= 1 the tiles peer r
+// pushed into the head's present_gather (`parts_* + (r - 1) * stride`).
+template <bool Gathered>
+__global__ void __launch_bounds__(256) rz_present_kernel(const uint32_t* own_rgba8, const float* own_depth, const uint32_t* parts_rgba8,
+                                                         const float* parts_depth, size_t stride, uint32_t* rgba8, float* depth, uint32_t width,
+                                                         uint32_t height, uint32_t tiles_x, uint32_t n_tiles, uint32_t world, uint32_t rank0) {
+    const uint32_t part = Gathered ? blockIdx.y : 0u;
+    if (blockIdx.x * world + rank0 + part >= n_tiles) return;  // the higher shards own one tile less
+    uint32_t tx, ty;
+    shard_tile(blockIdx.x, tiles_x, rank0 + part, world, tx, ty);
+    const uint32_t xr = threadIdx.x & 31u, yr = threadIdx.x >> 5;
+    const uint32_t x = tx * 32u + xr, y = ty * 8u + yr;
+    if (x >= width || y >= height) return;
+    const size_t src = size_t(blockIdx.x) * 256u + (xr >> 3) * 64u + yr * 8u + (xr & 7u);
+    uint32_t c;
+    float d;
+    if (Gathered && part != 0u) {
+        c = parts_rgba8[(part - 1u) * stride + src];
+        d = parts_depth[(part - 1u) * stride + src];
+    } else {
+        c = own_rgba8[src];
+        d = own_depth[src];
+    }
+    const size_t o = size_t(y) * width + x;
+    rgba8[o] = c;
+    depth[o] = d;
 }
 
 // Device self-test: div_shared() must equal the correctly rounded `/` bit for bit over its
@@ -506,6 +549,40 @@ int allocate_frame(hiprz_ctx* c) {
 }
 
 bool resident_active(const hiprz_ctx* c) { return c->pipeline == 2; }
+
+// hiprz_present's frame slots of one camera: freed only after the copy stream has finished with them
+void release_present(hiprz_ctx* c, hiprz_frame_state* f) {
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    for (auto& s : f->frame_slot) {
+        s.dev.release();
+        if (s.host) (void)hipHostFree(s.host);
+        if (s.ready) (void)hipEventDestroy(s.ready);
+        if (s.copied) (void)hipEventDestroy(s.copied);
+        s = hiprz_frame_state::FrameSlot{};
+    }
+    f->presented = 0u;
+}
+// the multi-part head's staging of its peers' tiles for a present: (parts - 1) slices of rgba8 then as many of depth
+int size_present_gather(hiprz_ctx* c) {
+    if (c->peers.empty() || c->shard_mode == HIPRZ_SHARD_SAMPLES || !c->have_camera) return HIPRZ_OK;
+    const size_t stride = size_t(c->n_local_tiles) * 256u;
+    RZ_HIP(c, c->present_gather.resize(stride * c->peers.size() * (sizeof(uint32_t) + sizeof(float))));
+    return HIPRZ_OK;
+}
+// the selected camera's frame slots for its (new) size; the sequence restarts
+int allocate_present(hiprz_ctx* c) {
+    if (c->is_peer) return HIPRZ_OK;
+    release_present(c, c);
+    if (!c->copy_stream) RZ_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    const size_t bytes = size_t(c->camera.width) * c->camera.height * (sizeof(uint32_t) + sizeof(float)) + 4u * sizeof(int32_t);
+    for (auto& s : c->frame_slot) {
+        RZ_HIP(c, s.dev.resize(bytes));
+        RZ_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&s.host), bytes, hipHostMallocDefault));
+        RZ_HIP(c, hipEventCreateWithFlags(&s.ready, hipEventDisableTiming));
+        RZ_HIP(c, hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+    }
+    return size_present_gather(c);
+}
 
 }  // namespace
 
@@ -1244,6 +1321,7 @@ int hiprz_create_multi(hiprz_ctx** out, const int* device_ids, int n_devices) {
             (void)hiprz_destroy(head);
             return fail(nullptr, rc, msg);
         }
+        peer->is_peer = true;
         head->peers.push_back(peer);
         if (device_ids[r] != device_ids[0]) {  // direct copies between the two GPUs (xGMI); absent peer access hip stages them through the host
             int can = 0;
@@ -1281,6 +1359,7 @@ int hiprz_set_camera_count(hiprz_ctx* c, uint32_t n) {
     RZ_HIP(c, hipStreamSynchronize(c->stream));
     for (uint32_t k = n; k < uint32_t(c->parked.size()); ++k) {
         if (c->parked[k].graph_exec) (void)hipGraphExecDestroy(c->parked[k].graph_exec);
+        release_present(c, &c->parked[k]);
         release_frame(&c->parked[k]);
         c->parked[k].pass_dev.release();
     }
@@ -1316,6 +1395,7 @@ int hiprz_destroy(hiprz_ctx* c) {
     for (uint32_t k = 0; k < uint32_t(c->parked.size()); ++k) {  // every camera's frame
         if (k == c->active_camera) continue;
         if (c->parked[k].graph_exec) (void)hipGraphExecDestroy(c->parked[k].graph_exec);
+        release_present(c, &c->parked[k]);
         release_frame(&c->parked[k]);
         c->parked[k].pass_dev.release();
     }
@@ -1338,8 +1418,11 @@ int hiprz_destroy(hiprz_ctx* c) {
     c->shadow_nodes64.release(), c->shadow_order.release();
     c->build_sort.keys_out.release(), c->build_sort.vals_a.release(), c->build_sort.vals_b.release(), c->build_sort.counts.release(), c->build_sort.row_total.release();
     c->texels.release(), c->spot_lights.release(), c->direct_lights.release();
+    release_present(c, c);
     release_frame(c);
-    c->pass_dev.release(), c->counters_dev.release(), c->pick_dev.release();
+    c->pass_dev.release(), c->counters_dev.release(), c->pick_dev.release(), c->present_gather.release();
+    if (c->present_consumed) (void)hipEventDestroy(c->present_consumed);
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return HIPRZ_OK;
@@ -1970,7 +2053,8 @@ int hiprz_upload_camera(hiprz_ctx* c, const hiprz_camera* cam) {
     d.focal_distance = cam->focal_distance, d.aperture = cam->aperture, d.exposure_time = cam->exposure_time;
     c->have_camera = true;
     if (resized) {
-        const int rc = allocate_frame(c);
+        int rc = allocate_frame(c);
+        if (rc == HIPRZ_OK) rc = allocate_present(c);
         if (rc != HIPRZ_OK) return rc;
     }
     c->reset_pending = true;  // camera changed => context.reset (cpu_engine_renderer.cpp:108-112)
@@ -2014,7 +2098,8 @@ int set_shard_one(hiprz_ctx* c, uint32_t rank, uint32_t world) {
     for (uint32_t k = 0; k < uint32_t(c->parked.size()); ++k) {  // every camera's frame is re-tiled for the new shard
         select_camera_one(c, k);
         if (c->have_camera) {
-            const int rc = allocate_frame(c);
+            int rc = allocate_frame(c);
+            if (rc == HIPRZ_OK) rc = size_present_gather(c);
             if (rc != HIPRZ_OK) return rc;
             c->reset_pending = true;
         }
@@ -2451,6 +2536,107 @@ int hiprz_pick(hiprz_ctx* c, uint32_t x, uint32_t y, int32_t* instance_out, int3
     const int rc = hiprz_ray_cast(c, x, y, &r);
     *instance_out = rc == HIPRZ_OK ? r.instance : -1, *material_out = rc == HIPRZ_OK ? r.material : -1;
     return rc;
+}
+
+// Render stream: tone map, (peers' pushes,) present kernel + pick into the slot, `ready`.  Copy stream: waits for `ready`, one copy of the
+// slot to its pinned twin, `copied`.  The render stream waits for a slot's previous `copied` before it writes that slot again.
+int hiprz_present(hiprz_ctx* c, uint32_t x, uint32_t y) {
+    if (!c) return HIPRZ_ERR_INVALID;
+    if (c->is_peer) return fail(c, HIPRZ_ERR_STATE, "present on a part of a multi-device context");
+    if (!c->have_scene || !c->have_camera) return fail(c, HIPRZ_ERR_STATE, "present before scene and camera upload");
+    if (!c->frame_slot[0].host || !c->copy_stream) return fail(c, HIPRZ_ERR_STATE, "present: the camera has no frame slots");
+    (void)hipSetDevice(c->device);
+    for (const auto& s : c->frame_slot)  // a copy of an earlier present that failed on the device
+        if (s.copy_enqueued) {
+            const hipError_t e = hipEventQuery(s.copied);
+            if (e != hipSuccess && e != hipErrorNotReady) return fail(c, HIPRZ_ERR_DEVICE, std::string("present: frame copy: ") + hipGetErrorString(e));
+        }
+    if (const int rc = hiprz_tonemap(c); rc != HIPRZ_OK) return rc;
+    (void)hipSetDevice(c->device);
+    const uint32_t sequence = c->presented + 1u;
+    hiprz_frame_state::FrameSlot& slot = c->frame_slot[(sequence - 1u) & 1u];
+    if (slot.copy_enqueued) RZ_HIP(c, hipStreamWaitEvent(c->stream, slot.copied, 0));
+    const uint32_t W = c->camera.width, H = c->camera.height;
+    const size_t n = size_t(W) * H;
+    uint32_t* rgba8 = reinterpret_cast<uint32_t*>(slot.dev.ptr);
+    float* depth = reinterpret_cast<float*>(rgba8 + n);
+    int32_t* record = reinterpret_cast<int32_t*>(depth + n);
+    // pixels of shards rendered elsewhere (hiprz_set_shard by the caller) stay zero, as in hiprz_read_*
+    if (c->user_world > 1u) RZ_HIP(c, hipMemsetAsync(slot.dev.ptr, 0, n * (sizeof(uint32_t) + sizeof(float)), c->stream));
+    const uint32_t n_tiles = c->tiles_x * c->tiles_y;
+    if (c->peers.empty() || c->shard_mode == HIPRZ_SHARD_SAMPLES) {  // (sample mode: the head's summed tone map and its depth)
+        if (c->n_local_tiles)
+            RZ_LAUNCH((rz_present_kernel<false>), dim3(c->n_local_tiles), dim3(256), 0, c->stream, c->rgba8.ptr, c->depth.ptr, nullptr, nullptr,
+                      size_t(0), rgba8, depth, W, H, c->tiles_x, n_tiles, c->world, c->rank);
+    } else {
+        // every peer pushes its tiles into its slices of the head's present_gather on ITS stream, behind its own tone map, once the
+        // previous present kernel has read them (present_consumed); the head's stream waits for all of them
+        const uint32_t n_parts = uint32_t(c->peers.size()) + 1u;
+        const size_t stride = size_t(c->n_local_tiles) * 256u;  // the head owns the lowest rank of the context: no shard has more tiles
+        if (c->present_gather.count < stride * (n_parts - 1u) * (sizeof(uint32_t) + sizeof(float)))
+            return fail(c, HIPRZ_ERR_STATE, "present: the staging of the parts' tiles is not sized for this shard");
+        uint32_t* parts_rgba8 = reinterpret_cast<uint32_t*>(c->present_gather.ptr);
+        float* parts_depth = reinterpret_cast<float*>(parts_rgba8 + stride * (n_parts - 1u));
+        if (!c->present_consumed) RZ_HIP(c, hipEventCreateWithFlags(&c->present_consumed, hipEventDisableTiming));
+        for (uint32_t r = 1; r < n_parts; ++r) {
+            hiprz_ctx* p = c->peers[r - 1u];
+            const size_t local = size_t(p->n_local_tiles) * 256u;
+            if (!local) continue;
+            (void)hipSetDevice(p->device);
+            if (c->consumed_recorded) RZ_HIP(c, hipStreamWaitEvent(p->stream, c->present_consumed, 0));
+            RZ_HIP(c, hipMemcpyPeerAsync(parts_rgba8 + stride * (r - 1u), c->device, p->rgba8.ptr, p->device, local * sizeof(uint32_t), p->stream));
+            RZ_HIP(c, hipMemcpyPeerAsync(parts_depth + stride * (r - 1u), c->device, p->depth.ptr, p->device, local * sizeof(float), p->stream));
+            RZ_HIP(c, hipEventRecord(p->peer_done, p->stream));
+            (void)hipSetDevice(c->device);
+            RZ_HIP(c, hipStreamWaitEvent(c->stream, p->peer_done, 0));
+        }
+        if (c->n_local_tiles)
+            RZ_LAUNCH((rz_present_kernel<true>), dim3(c->n_local_tiles, n_parts), dim3(256), 0, c->stream, c->rgba8.ptr, c->depth.ptr, parts_rgba8,
+                      parts_depth, stride, rgba8, depth, W, H, c->tiles_x, n_tiles, c->world, c->rank);
+        RZ_HIP(c, hipEventRecord(c->present_consumed, c->stream));
+        c->consumed_recorded = true;
+    }
+    // the ray cast of hiprz_ray_cast: clamped pixel (camera.cpp:159-165), answered where some part of this context rendered it
+    if (x >= W) x = W - 1u;
+    if (y >= H) y = H - 1u;
+    uint32_t owner, lt;
+    shard_of_tile(x / 32u, y / 8u, c->tiles_x, c->world, owner, lt);
+    bool owned = owner == c->rank;
+    for (hiprz_ctx* p : c->peers) owned = owned || (p->world == c->world && owner == p->rank);
+    RZ_LAUNCH(rz_pick_slot_kernel, dim3(1), dim3(1), 0, c->stream, c->dscene, c->dcamera, x, y, uint32_t(owned), depth, record);
+    RZ_HIP(c, hipGetLastError());
+    RZ_HIP(c, hipEventRecord(slot.ready, c->stream));
+    RZ_HIP(c, hipStreamWaitEvent(c->copy_stream, slot.ready, 0));
+    RZ_HIP(c, hipMemcpyAsync(slot.host, slot.dev.ptr, n * (sizeof(uint32_t) + sizeof(float)) + 4u * sizeof(int32_t), hipMemcpyDeviceToHost, c->copy_stream));
+    RZ_HIP(c, hipEventRecord(slot.copied, c->copy_stream));
+    slot.copy_enqueued = true;
+    slot.sequence = sequence, slot.passes = c->passes;
+    slot.ray_count = c->ray_count;  // hiprz_ray_count
+    for (hiprz_ctx* p : c->peers) slot.ray_count += p->ray_count;
+    c->presented = sequence;
+    return HIPRZ_OK;
+}
+
+int hiprz_read_frame(hiprz_ctx* c, uint32_t sequence, hiprz_frame* out) {
+    if (!c) return HIPRZ_ERR_INVALID;
+    if (!out) return fail(c, HIPRZ_ERR_INVALID, "read_frame: null output");
+    if (c->presented == 0u) return fail(c, HIPRZ_ERR_STATE, "read_frame: nothing presented on this camera since it was sized");
+    if (sequence == 0u) sequence = c->presented;
+    if (sequence > c->presented || sequence + 1u < c->presented)
+        return fail(c, HIPRZ_ERR_STATE, "read_frame: sequence " + std::to_string(sequence) + " is not one of the newest two (" +
+                                            std::to_string(c->presented) + ")");
+    const hiprz_frame_state::FrameSlot& slot = c->frame_slot[(sequence - 1u) & 1u];
+    if (slot.sequence != sequence || !slot.copy_enqueued) return fail(c, HIPRZ_ERR_STATE, "read_frame: sequence not presented");
+    (void)hipSetDevice(c->device);
+    RZ_HIP(c, hipEventSynchronize(slot.copied));
+    const size_t n = size_t(c->camera.width) * c->camera.height;
+    const int32_t* record = reinterpret_cast<const int32_t*>(slot.host + n * (sizeof(uint32_t) + sizeof(float)));
+    out->rgba8 = slot.host;
+    out->depth = reinterpret_cast<const float*>(slot.host + n * sizeof(uint32_t));
+    out->width = c->camera.width, out->height = c->camera.height;
+    out->passes = slot.passes, out->sequence = slot.sequence, out->ray_count = slot.ray_count;
+    out->hit = hiprz_raycast{record[0], record[1], record[2], uint32_t(record[3])};
+    return HIPRZ_OK;
 }
 
 uint32_t hiprz_kernel_count(void) { return uint32_t(kernel_table().size()); }

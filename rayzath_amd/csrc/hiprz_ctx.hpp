@@ -157,6 +157,18 @@ struct hiprz_frame_state {
     float temporal_blend = 0.75f;
     hiprz::DeviceArray<uint8_t> gather;  // multi-device head: the peers' tile buffers land here before one launch untiles them all
     hiprz::DeviceArray<float4> sum_accum;  // HIPRZ_SHARD_SAMPLES head: the parts' accumulators summed, tile-major like `accum`
+    // hiprz_present: two frame slots per camera, each `rgba8 | depth | 16-byte ray-cast record` on the device and as pinned host memory,
+    // allocated when the camera is uploaded at a new size (allocate_present), never by a present
+    struct FrameSlot {
+        hiprz::DeviceArray<uint8_t> dev;
+        uint8_t* host = nullptr;
+        hipEvent_t ready = nullptr;   // render stream: the slot is assembled (the copy stream waits for it)
+        hipEvent_t copied = nullptr;  // copy stream: the slot has reached `host` (hiprz_read_frame waits for it, the next present into the slot too)
+        bool copy_enqueued = false;
+        uint32_t sequence = 0, passes = 0;
+        uint64_t ray_count = 0;
+    } frame_slot[2];
+    uint32_t presented = 0;  // sequence of the newest present (0: none since the camera was sized)
 };
 
 struct hiprz_ctx : hiprz_frame_state {
@@ -177,6 +189,13 @@ struct hiprz_ctx : hiprz_frame_state {
     uint32_t shard_mode = 0;          // HIPRZ_SHARD_TILES | HIPRZ_SHARD_SAMPLES (head): how the parts divide the context's share
     hipEvent_t sum_done = nullptr;    // head, sample mode: the last sum of the parts has read the staging slices (the peers' next copies wait for it)
     bool sum_recorded = false;
+    bool is_peer = false;             // a part of a multi-device context: presents nothing, owns no frame slots
+    // hiprz_present: the copy stream moves assembled frame slots to the host beside the render stream; a multi-part head's peers push
+    // their tiles into present_gather, and their next push waits for present_consumed (the present kernel has read the slices)
+    hipStream_t copy_stream = nullptr;
+    hiprz::DeviceArray<uint8_t> present_gather;
+    hipEvent_t present_consumed = nullptr;
+    bool consumed_recorded = false;
 
     // cameras (hiprz_set_camera_count / hiprz_select_camera)
     std::vector<hiprz_frame_state> parked;  // slot [active_camera] is empty while that camera's state lives in the context itself

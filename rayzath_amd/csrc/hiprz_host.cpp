@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -352,6 +353,10 @@ void hiprz_abi_sizes(uint32_t out[13]) {
                             sizeof(hiprz_scene),  sizeof(hiprz_camera),   sizeof(hiprz_config),     sizeof(hiprz_counters),
                             sizeof(hiprz_mesh_desc)};
     std::memcpy(out, v, sizeof v);
+}
+
+void hiprz_frame_layout(uint32_t out[3]) {
+    out[0] = sizeof(hiprz_frame), out[1] = offsetof(hiprz_frame, ray_count), out[2] = offsetof(hiprz_frame, hit);
 }
 
 const char* hiprz_version(void) { return "hiprz 0.1 (gfx950)"; }

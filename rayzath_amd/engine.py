@@ -67,6 +67,7 @@ class Context:
             raise HiprzError(rc, (self.lib.hiprz_last_error(None) or b"").decode())
         self.width = self.height = 0
         self._sizes = {}
+        self._presented = {}  # camera -> sequence of its newest present
 
     def device_count(self):
         v = C.c_uint32()
@@ -76,6 +77,7 @@ class Context:
     # --- cameras: one frame state each, the calls below address the selected one ---
     def set_camera_count(self, n):
         self._check(self.lib.hiprz_set_camera_count(self._ctx, n))
+        self._presented = {k: v for k, v in self._presented.items() if k < n}
 
     def camera_count(self):
         v = C.c_uint32()
@@ -120,6 +122,8 @@ class Context:
 
     def upload_camera(self, camera_struct_):
         self._check(self.lib.hiprz_upload_camera(self._ctx, C.byref(camera_struct_)))
+        if (self.width, self.height) != (camera_struct_.width, camera_struct_.height):
+            self._presented[getattr(self, "_camera", 0)] = 0  # a resize restarts the camera's sequence
         self.width, self.height = camera_struct_.width, camera_struct_.height
 
     def set_config(self, config_struct):
@@ -277,6 +281,29 @@ class Context:
         self._check(self.lib.hiprz_ray_cast(self._ctx, x, y, C.byref(r)))
         return r.instance, r.material_slot, r.material, r.triangle
 
+    # --- pipelined frame delivery ---
+    def present(self, x=0, y=0):
+        """hiprz_present: enqueue the selected camera's frame (tone map, rgba8 + depth + the ray cast through pixel (x, y)) for the copy to
+        pinned host memory; never waits for the GPU.  Returns the frame's sequence number."""
+        self._check(self.lib.hiprz_present(self._ctx, int(x), int(y)))
+        cam = getattr(self, "_camera", 0)
+        self._presented[cam] = self._presented.get(cam, 0) + 1  # as the context counts: 1, 2, ... per camera, from 1 again after a resize
+        return self._presented[cam]
+
+    def read_frame(self, seq=0, copy=False):
+        """hiprz_read_frame: waits for that frame's copy.  Returns dict(rgba8 (H, W, 4) u8, depth (H, W) f32, width, height, passes,
+        sequence, ray_count, hit=(instance, material slot, material, triangle)).  The arrays are views of the context's pinned memory, valid
+        until the second present after this one on the camera (or a resize): copy=True returns arrays of their own."""
+        f = _abi.Frame()
+        self._check(self.lib.hiprz_read_frame(self._ctx, int(seq), C.byref(f)))
+        h, w = f.height, f.width
+        rgba8 = np.ctypeslib.as_array(f.rgba8, shape=(h, w, 4))
+        depth = np.ctypeslib.as_array(f.depth, shape=(h, w))
+        if copy:
+            rgba8, depth = rgba8.copy(), depth.copy()
+        return dict(rgba8=rgba8, depth=depth, width=w, height=h, passes=f.passes, sequence=f.sequence, ray_count=f.ray_count,
+                    hit=(f.hit.instance, f.hit.material_slot, f.hit.material, f.hit.triangle))
+
     def selftest(self, cases_per_thread=64, seed=1):
         bad, n = C.c_uint64(), C.c_uint64()
         self._check(self.lib.hiprz_selftest(self._ctx, cases_per_thread, seed, C.byref(bad), C.byref(n)))
@@ -353,10 +380,14 @@ class Engine:
 
     REBUILD_EVERY = 16   # moved frames (World.mark_moved) between two device rebuilds of the refitted trees
 
-    def __init__(self, device=0, streams=None):
+    def __init__(self, device=0, streams=None, pipelined=False):
         """`device`: a GPU id, or a list of ids (one context over several GPUs).  `streams` (single GPU only): how many contexts share
-        the GPU, None = default_streams() of the first world rendered; asking for `engine.context` before that settles for one."""
+        the GPU, None = default_streams() of the first world rendered; asking for `engine.context` before that settles for one.
+        `pipelined`: frames leave through Context.present / read_frame, and renderWorld(sync=False) hands out the PREVIOUS call's frame
+        while this call's renders (the C++ engine's sync=false); the default reads every frame synchronously and ignores `sync`."""
         self._device, self._streams, self._context = device, streams, None
+        self._pipelined = pipelined
+        self._pending = []  # pipelined, sync=False: (camera slot, camera, sequence) presented by the previous call, not yet handed out
         self._tree = TREE_AUTO   # the hosts' default: the snapshot's trees for scenes staged in LDS, the device's surface-area trees otherwise
         self.backend = HostBackend(_lib.load())
         self._world_key = None
@@ -419,7 +450,13 @@ class Engine:
             world._dirty = False
         ctx.set_config(render_config.struct())
         cameras = [c for c in [world.camera] + list(getattr(world, "cameras", [])) if getattr(c, "enabled", True)]
+        pending, self._pending = self._pending, []
         if [id(c) for c in cameras] != self._camera_ids:  # one frame state per enabled camera, in the reference's order
+            for k, cam, seq in pending:  # the previous call's frames go out before their camera slots are rearranged
+                if any(cam is c for c in cameras):
+                    ctx.select_camera(k)
+                    self._deliver(ctx, cam, world, ctx.read_frame(seq))
+            pending = []
             ctx.set_camera_count(max(len(cameras), 1))
             self._camera_ids, self._camera_key = [id(c) for c in cameras], {}
         for k, cam in enumerate(cameras):
@@ -427,10 +464,23 @@ class Engine:
             cam_key = (cam.width, cam.height, cam.position.tobytes(), cam.rotation.tobytes(), cam.fov, cam.near_far,
                        cam.focal_distance, cam.aperture, cam.exposure_time)
             if self._camera_key.get(k) != cam_key:
+                resized = self._camera_key.get(k, (None, None))[:2] != cam_key[:2]
+                for item in [q for q in pending if q[0] == k and resized]:  # a resize frees the camera's frame slots: its frame goes out first
+                    pending.remove(item)
+                    if item[1] is cam:
+                        self._deliver(ctx, cam, world, ctx.read_frame(item[2]))
                 ctx.upload_camera(camera_struct(cam, self.backend))
                 ctx.set_temporal_blend(cam.temporal_blend)
                 self._camera_key[k] = cam_key
             ctx.render(max(render_config.tracing.rpp, 1))
+            if self._pipelined:
+                px, py = getattr(cam, "ray_cast_pixel", (0, 0))
+                seq = ctx.present(int(px), int(py))  # enqueue only
+                if sync:
+                    self._deliver(ctx, cam, world, ctx.read_frame(seq))
+                else:
+                    self._pending.append((k, cam, seq))
+                continue
             ctx.tonemap()
             cam.image_buffer = ctx.read_rgba8()  # synchronises
             cam.depth_buffer = ctx.read_depth()
@@ -441,6 +491,24 @@ class Engine:
             cam.raycasted_instance = world.instances[inst] if 0 <= inst < len(world.instances) else None
             materials = getattr(cam.raycasted_instance, "materials", None) or []
             cam.raycasted_material = materials[slot] if cam.raycasted_instance is not None and 0 <= slot < len(materials) else None
+        if self._pipelined and not sync:  # every camera's render is enqueued: hand out the previous call's frames (the first call has none)
+            for k, cam, seq in pending:
+                if any(cam is c for c in cameras):
+                    ctx.select_camera(k)
+                    self._deliver(ctx, cam, world, ctx.read_frame(seq))
+            if pending and cameras:
+                ctx.select_camera(len(cameras) - 1)
+
+    @staticmethod
+    def _deliver(ctx, cam, world, frame):
+        """a frame of Context.read_frame into the camera, as the synchronous path fills it"""
+        cam.image_buffer = frame["rgba8"].copy()
+        cam.depth_buffer = frame["depth"].copy()
+        cam.ray_count = frame["ray_count"]
+        inst, slot, _, _ = frame["hit"]
+        cam.raycasted_instance = world.instances[inst] if 0 <= inst < len(world.instances) else None
+        materials = getattr(cam.raycasted_instance, "materials", None) or []
+        cam.raycasted_material = materials[slot] if cam.raycasted_instance is not None and 0 <= slot < len(materials) else None
 
     def timingsString(self):
         return self.context.timings()
