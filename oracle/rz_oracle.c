@@ -28,6 +28,7 @@
 #define RZ_ATAN2F(y, x) atan2f(y, x)
 #define RZ_POWF(x, y) powf(x, y)
 #define RZ_EXPF(x) expf(x)
+#define RZ_LOGF(x) logf(x)
 const char* rzo_math_mode(void) { return "libm"; }
 
 #define RZ_PI 3.14159265358979323846f /* std::numbers::pi_v<float> */
@@ -160,6 +161,7 @@ typedef struct {
     const hiprz_camera* cam;
     const hiprz_config* cfg;
     hiprz_counters* cnt; /* per-thread, may be NULL */
+    uint32_t flags;      /* HIPRZ_COMPAT_* (rzo_render_pass_mode); 0 = the CPU engine */
 } kctx;
 
 #define COUNT(k, field, n) \
@@ -434,6 +436,8 @@ static void map_normal(const hiprz_tri* tri, const hiprz_tri_attr* at, col map_c
                             v3_scale(bitangent, map_n.y));
 }
 
+static col compat_map(const kctx* k, int32_t tex_idx, float u, float v); /* CUDA-compat section below */
+
 static void analyze_intersection(const kctx* k, const traversal_t* tr, surface_t* sf) {
     const hiprz_scene* s = k->s;
     const hiprz_instance* in = &s->instances[tr->closest_instance];
@@ -468,7 +472,9 @@ static void analyze_intersection(const kctx* k, const traversal_t* tr, surface_t
     /* The reference indexes mesh.texcrds() unconditionally inside mapNormal (UB for a
      * triangle without texcrds); such triangles are shaded here as if unmapped. */
     if (m->normal_map >= 0 && has_texcrds) {
-        map_normal(tri, at, fetch_rgba8(k, m->normal_map, sf->u, sf->v), &sf->mapped_normal, v3_from(in->scale));
+        const col map_color = (k->flags & HIPRZ_COMPAT_FILTERING) ? compat_map(k, m->normal_map, sf->u, sf->v)
+                                                                   : fetch_rgba8(k, m->normal_map, sf->u, sf->v);
+        map_normal(tri, at, map_color, &sf->mapped_normal, v3_from(in->scale));
         sf->mapped_normal = transform_l2g_noscale(in, sf->mapped_normal);
     } else {
         sf->mapped_normal = transform_l2g(in, sf->mapped_normal);
@@ -579,6 +585,249 @@ static float any_intersection(const kctx* k, const ray_t* ray) {
     float mask = 1.0f;
     any_world(k, s->tlas_root, ray, &mask);
     return mask;
+}
+
+/* ====================================================================================
+ * CUDA-compat mode (rzo_render_pass_mode, HIPRZ_COMPAT_* of hiprz.h) — what the
+ * reference's CUDA engine computes and its CPU engine does not.  Restated from the CUDA
+ * text, not from the HIP kernel:
+ *   HIPRZ_COMPAT_BEER_LAMBERT  traceRay, cuda_render_kernel.cu:146-176
+ *   HIPRZ_COMPAT_SCATTERING    World::closestIntersection cuda_world.cuh:91-100,
+ *                              Material::applyScattering cuda_material.cuh:141-159
+ *   HIPRZ_COMPAT_SHADOW_COLOR  World/Instance/Mesh::anyIntersection cuda_bvh.cuh:172-232,
+ *                              cuda_instance.cuh:92-164, 215-229; used as V_PL * V_PL.alpha
+ *                              (cuda_render_kernel.cu:282-288)
+ *   HIPRZ_COMPAT_TEXTURE_MULT  Material::color / opacityColor / emission, cuda_material.cuh:75-123
+ *   HIPRZ_COMPAT_FILTERING     TextureBuffer::fetch, cuda_buffer.cuh:364-438 (tex2D, normalised
+ *                              coordinates, filter and address modes of the texture object)
+ * HIPRZ_COMPAT_REPROJECTION acts on the frame at a restart, not in the integrator; it is not
+ * restated here.
+ *
+ * Where the HIP compat path departs from the CUDA text ON PURPOSE, this restatement follows
+ * the HIP design (the same list is in DESIGN.md, CUDA-compat section):
+ *   D1  the random numbers are the CPU engine's RNG with the harness seeding (pixel_rng),
+ *       not CUDA's; the scattering distance is the FIRST draw of a segment's stream.
+ *   D2  linear-filter weights are computed in float; CUDA hardware uses 8-bit fractions
+ *       (CUDA C Programming Guide, "Texture Fetching": 9-bit fixed point, 8 fractional bits).
+ *   D3  address modes act on the integer texel index of each tap (point: floor(u * w);
+ *       linear: floor(u * w - 0.5) and +1); the CUDA guide states wrap / mirror on the
+ *       normalised coordinate.  The two agree except where frac(u) * w rounds.
+ *   D4  texel indices are exact for |u * w| < 2^30; a coordinate beyond that (or a NaN) is
+ *       clamped to -2^30 / +2^30 before the float -> int conversion.
+ *   D5  without HIPRZ_COMPAT_FILTERING a map is read as the CPU engine reads it (point, wrap,
+ *       render_parts.hpp:209-221); without HIPRZ_COMPAT_TEXTURE_MULT a texture / emission map
+ *       replaces the colour / emission (cpu_engine_kernel.cpp:505-528).
+ *   D6  a crossed triangle's material is instance.material(id) of the CPU engine (slot
+ *       clamped to 63, unset -> default), and the triangle test is the CPU engine's.
+ * Not a departure: every segment that meets no object gets the sky's texcrd
+ * (calculateTexcrd, cuda_world.cuh:86-88), also when the ray misses the world's root box,
+ * where the CPU engine keeps (0, 0) (cpu_engine_kernel.cpp:279-298).
+ * The split pipeline's deferred mask kernels (any_hit_coop_mask, any_hit_packet) depart
+ * from the grouping restated here: they multiply in their own walk's order and take the
+ * 1e-4 early-out on the running mask.  This restatement does not follow them; the tests
+ * bound what that changes (CUDA-compat section).
+ * ==================================================================================== */
+#define RZO_TEXEL_LIMIT 1073741824.0f /* 2^30 (D4) */
+static inline int compat_index(float x) {
+    return (int)floorf(fminf(fmaxf(x, -RZO_TEXEL_LIMIT), RZO_TEXEL_LIMIT));
+}
+/* one texel index under an address mode (cudaTextureAddressMode, cuda_buffer.cuh:366-386);
+ * *inside = 0 only for a border-mode access outside the image */
+static int compat_texel(int i, int n, uint32_t mode, int* inside) {
+    *inside = 1;
+    switch (mode) {
+        case HIPRZ_TEX_ADDRESS_CLAMP:
+            return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
+        case HIPRZ_TEX_ADDRESS_BORDER:
+            *inside = i >= 0 && i < n;
+            return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
+        case HIPRZ_TEX_ADDRESS_MIRROR: { /* period 2n: 0 .. n-1, then n-1 .. 0 */
+            int k = i % (2 * n);
+            if (k < 0) k += 2 * n;
+            return k < n ? k : (2 * n - 1) - k;
+        }
+        default: { /* wrap */
+            int k = i % n;
+            return k < 0 ? k + n : k;
+        }
+    }
+}
+/* one texel as a float4: uint8 kinds under cudaReadModeNormalizedFloat (/255), float as is
+ * (cudaReadModeElementType); the channels a 1-channel texture lacks read 0 */
+static col compat_load(const kctx* k, const hiprz_texture* tex, int x, int y) {
+    const size_t at = (size_t)y * tex->width + (size_t)x;
+    const uint8_t* base = k->s->texels + tex->offset;
+    if (tex->kind == HIPRZ_TEX_RGBA8) return col_from_u8(base + 4u * at);
+    if (tex->kind == HIPRZ_TEX_R8) return COL(base[at] / 255.0f, 0.0f, 0.0f, 0.0f);
+    float f;
+    memcpy(&f, base + 4u * at, 4);
+    return COL(f, 0.0f, 0.0f, 0.0f);
+}
+/* TextureBuffer::fetch, cuda_buffer.cuh:427-438: texcrd += translation; Rotate; *= scale;
+ * tex2D(x, 1 - y) with normalisedCoords = 1 (:400).  Point: texel floor(x * w).  Linear:
+ * the four texels around x * w - 0.5, weighted by the fractions (D2, D3). */
+static col compat_fetch(const kctx* k, int32_t tex_idx, float u, float v) {
+    const hiprz_texture* tex = &k->s->textures[tex_idx];
+    const uint32_t address = tex->sampling & 0xFF00u;
+    u += tex->translation[0];
+    v += tex->translation[1];
+    { /* vec2::Rotate (cuda_render_parts.cuh:373-381) */
+        const float xx = u * tex->cos_rotation - v * tex->sin_rotation;
+        const float yy = u * tex->sin_rotation + v * tex->cos_rotation;
+        u = xx * tex->scale[0];
+        v = 1.0f - yy * tex->scale[1];
+    }
+    COUNT(k, texel_fetches, 1);
+    const int w = (int)tex->width, h = (int)tex->height;
+    int in_x, in_y;
+    if ((tex->sampling & 0xFFu) != HIPRZ_TEX_FILTER_LINEAR) { /* cudaFilterModePoint (:388-396) */
+        const int x = compat_texel(compat_index(u * (float)w), w, address, &in_x);
+        const int y = compat_texel(compat_index(v * (float)h), h, address, &in_y);
+        return in_x && in_y ? compat_load(k, tex, x, y) : col_splat(0.0f);
+    }
+    /* cudaFilterModeLinear: tex(x, y) = (1-a)(1-b) T[i, j] + a(1-b) T[i+1, j] + (1-a) b T[i, j+1] + a b T[i+1, j+1] */
+    const float fx = fminf(fmaxf(u * (float)w - 0.5f, -RZO_TEXEL_LIMIT), RZO_TEXEL_LIMIT);
+    const float fy = fminf(fmaxf(v * (float)h - 0.5f, -RZO_TEXEL_LIMIT), RZO_TEXEL_LIMIT);
+    const int x0 = (int)floorf(fx), y0 = (int)floorf(fy);
+    const float ax = fx - (float)x0, ay = fy - (float)y0;
+    col sum = col_splat(0.0f);
+    for (int tap = 0; tap < 4; ++tap) {
+        const int x = compat_texel(x0 + (tap & 1), w, address, &in_x);
+        const int y = compat_texel(y0 + (tap >> 1), h, address, &in_y);
+        const float wgt = ((tap & 1) ? ax : 1.0f - ax) * ((tap >> 1) ? ay : 1.0f - ay);
+        if (in_x && in_y) sum = col_add(sum, col_scale(compat_load(k, tex, x, y), wgt));
+    }
+    return sum;
+}
+/* a map as the compat integrator reads it: the texture object's modes under
+ * HIPRZ_COMPAT_FILTERING, the CPU engine's point / wrap read otherwise (D5) */
+static col compat_map(const kctx* k, int32_t tex_idx, float u, float v) {
+    if (k->flags & HIPRZ_COMPAT_FILTERING) return compat_fetch(k, tex_idx, u, v);
+    switch (k->s->textures[tex_idx].kind) {
+        case HIPRZ_TEX_RGBA8: return fetch_rgba8(k, tex_idx, u, v);
+        case HIPRZ_TEX_R8: return COL((float)fetch_r8(k, tex_idx, u, v) / 255.0f, 0.0f, 0.0f, 0.0f);
+        default: return COL(fetch_r32f(k, tex_idx, u, v), 0.0f, 0.0f, 0.0f);
+    }
+}
+/* Material::opacityColor(texcrd), cuda_material.cuh:80-95 */
+static col compat_opacity_color(const kctx* k, const hiprz_material* m, float u, float v) {
+    col c = col_from_u8(m->color);
+    c.a = 1.0f - c.a;
+    if (m->texture < 0) return c;
+    col t = compat_map(k, m->texture, u, v);
+    t.a = 1.0f - t.a;
+    return col_mul(c, t);
+}
+/* Material::emission(texcrd), cuda_material.cuh:114-123 */
+static float compat_emission(const kctx* k, const hiprz_material* m, float u, float v) {
+    float e = m->emission;
+    if (m->emission_map >= 0) e *= compat_map(k, m->emission_map, u, v).r;
+    return e;
+}
+
+/* Mesh::anyIntersection, cuda_instance.cuh:92-164: the mesh's own mask, the product of
+ * opacityColor(texcrd) of every triangle the ray crosses, children in the order begin,
+ * begin + 1; it returns as soon as ITS alpha drops below 1e-4.  Returns 1 on that early
+ * return. */
+static int compat_mesh_node(const kctx* k, const hiprz_instance* in, const hiprz_node* node, const ray_t* ray, col* mask) {
+    if (node_is_leaf(node)) {
+        const uint32_t end = node->begin + node_count(node);
+        for (uint32_t i = node->begin; i < end; ++i) {
+            const hiprz_tri* tri = &k->s->tris[i];
+            float t, b1, b2, det;
+            COUNT(k, tri_tests, 1);
+            COUNT(k, shadow_tri_tests, 1);
+            if (!tri_hit(tri, ray, &t, &b1, &b2, &det)) continue;
+            float u = 0.0f, v = 0.0f;
+            if (tri->material_flags & HIPRZ_TRI_HAS_TEXCRDS) { /* texcrdFromBarycenter, mesh_component.cpp:115-123 */
+                const hiprz_tri_attr* at = &k->s->tri_attrs[i];
+                const float b3 = 1.0f - b1 - b2;
+                u = at->t1[0] * b3 + at->t2[0] * b1 + at->t3[0] * b2;
+                v = at->t1[1] * b3 + at->t2[1] * b1 + at->t3[1] * b2;
+            }
+            uint32_t slot = tri->material_flags & HIPRZ_TRI_MATERIAL_MASK; /* D6 */
+            if (slot > 63u) slot = 63u;
+            int32_t mat = -1;
+            if (slot < in->material_count) mat = k->s->inst_materials[in->material_base + slot];
+            const hiprz_material* m = &k->s->materials[mat < 0 ? HIPRZ_MATERIAL_DEFAULT : (uint32_t)mat];
+            *mask = col_mul(*mask, compat_opacity_color(k, m, u, v));
+            if (mask->a < 1.0e-4f) return 1;
+        }
+        return 0;
+    }
+    for (uint32_t c = 0; c < 2u; ++c) {
+        const hiprz_node* child = &k->s->nodes[node->begin + c];
+        COUNT(k, box_tests, 1);
+        COUNT(k, shadow_box_tests, 1);
+        if (box_hit(child->bb_min, child->bb_max, ray) && compat_mesh_node(k, in, child, ray, mask)) return 1;
+    }
+    return 0;
+}
+/* Instance::anyIntersection, cuda_instance.cuh:215-229 (+ the root tests of :94-95) */
+static col compat_instance_mask(const kctx* k, uint32_t inst_idx, const ray_t* ray) {
+    const hiprz_instance* in = &k->s->instances[inst_idx];
+    col mask = col_splat(1.0f);
+    COUNT(k, box_tests, 1);
+    COUNT(k, shadow_box_tests, 1);
+    if (!box_hit(in->bb_min, in->bb_max, ray)) return mask;
+    ray_t local = *ray;
+    transform_g2l(in, &local);
+    const float len = v3_mag(local.direction);
+    local.near_ *= len;
+    local.far_ *= len;
+    local.direction = v3_normalized(local.direction);
+    const hiprz_node* root = &k->s->nodes[in->blas_root];
+    COUNT(k, box_tests, 1);
+    COUNT(k, shadow_box_tests, 1);
+    if (!box_hit(root->bb_min, root->bb_max, &local)) return mask;
+    compat_mesh_node(k, in, root, &local, &mask);
+    return mask;
+}
+/* World::anyIntersection -> ObjectContainerWithBVH::anyIntersection, cuda_bvh.cuh:172-232:
+ * the running mask is multiplied by each instance's whole mask, and the walk returns as soon
+ * as the RUNNING mask's alpha drops below 1e-4 */
+static int compat_world_node(const kctx* k, const hiprz_node* node, const ray_t* ray, col* mask) {
+    if (node_is_leaf(node)) {
+        const uint32_t end = node->begin + node_count(node);
+        for (uint32_t i = node->begin; i < end; ++i) {
+            *mask = col_mul(*mask, compat_instance_mask(k, k->s->tlas_order[i], ray));
+            if (mask->a < 0.0001f) return 1;
+        }
+        return 0;
+    }
+    for (uint32_t c = 0; c < 2u; ++c) {
+        const hiprz_node* child = &k->s->nodes[node->begin + c];
+        COUNT(k, box_tests, 1);
+        COUNT(k, shadow_box_tests, 1);
+        if (box_hit(child->bb_min, child->bb_max, ray) && compat_world_node(k, child, ray, mask)) return 1;
+    }
+    return 0;
+}
+static col compat_shadow_mask(const kctx* k, const ray_t* ray) {
+    col mask = col_splat(1.0f);
+    COUNT(k, shadow_rays, 1);
+    if (k->s->n_instances == 0) return mask; /* the tree is empty */
+    const hiprz_node* root = &k->s->nodes[k->s->tlas_root];
+    COUNT(k, box_tests, 1);
+    COUNT(k, shadow_box_tests, 1);
+    if (!box_hit(root->bb_min, root->bb_max, ray)) return mask;
+    compat_world_node(k, root, ray, &mask);
+    return mask;
+}
+/* the shadow mask V_PL the light samplers use: the CPU engine's 0 / 1 (any_intersection),
+ * or the coloured mask */
+static col shadow_mask(const kctx* k, const ray_t* ray) {
+    if (k->flags & HIPRZ_COMPAT_SHADOW_COLOR) return compat_shadow_mask(k, ray);
+    return col_splat(any_intersection(k, ray));
+}
+
+void rzo_compat_fetch(const hiprz_scene* scene, int32_t texture, float u, float v, float out[4], uint64_t* fetches) {
+    hiprz_counters cnt;
+    memset(&cnt, 0, sizeof cnt);
+    const kctx k = {scene, NULL, NULL, &cnt, HIPRZ_COMPAT_FILTERING};
+    const col c = compat_fetch(&k, texture, u, v);
+    out[0] = c.r, out[1] = c.g, out[2] = c.b, out[3] = c.a;
+    if (fetches) *fetches = cnt.texel_fetches;
 }
 
 /* ------------------------------------------------------------------------------------
@@ -792,8 +1041,7 @@ static col direct_light_sampling(const kctx* k, const ray_t* ray, v3 point, v3 n
         if (radiance < 1.0e-4f) continue;
 
         const ray_t sr = shadow_ray(point, vPL, 0.0f, FLT_MAX);
-        const float V = any_intersection(k, &sr);
-        const col V_PL = col_splat(V);
+        const col V_PL = shadow_mask(k, &sr); /* the CUDA engine's coloured mask: cuda_render_kernel.cu:282-288 */
         total = col_add(total,
                         col_scale(col_mul(col_scale(col_mul(col_from_u8(light->color), bc), radiance), V_PL), V_PL.a));
     }
@@ -856,8 +1104,7 @@ static col spot_light_sampling(const kctx* k, const ray_t* ray, v3 point, v3 nex
         if (radiance < 1.0e-4f) continue;
 
         const ray_t sr = shadow_ray(point, vPL, 0.0f, dPL);
-        const float V = any_intersection(k, &sr);
-        const col V_PL = col_splat(V);
+        const col V_PL = shadow_mask(k, &sr); /* the CUDA engine's coloured mask: cuda_render_kernel.cu:282-288 */
         total = col_add(total,
                         col_scale(col_mul(col_scale(col_mul(col_from_u8(light->color), bc), radiance), V_PL), V_PL.a));
     }
@@ -894,11 +1141,46 @@ static tracing_result trace_ray(const kctx* k, tracing_state* ts, ray_t* ray, rn
     sf.fresnel = 1.0f;
 
     COUNT(k, segments, 1);
-    const int any_hit = closest_intersection(k, ray, &sf, NULL);
+    int scattered = 0;
+    if (k->flags & HIPRZ_COMPAT_SCATTERING) { /* World::closestIntersection, cuda_world.cuh:91-100: the medium first */
+        const float sigma = k->s->materials[ray->material].scattering; /* Material::applyScattering, cuda_material.cuh:141-159 */
+        if (sigma > 1.0e-4f) {
+            const float scatter_distance = (-RZ_LOGF(rng_unsigned(rng) + 1.0e-4f)) / sigma;
+            if (scatter_distance < ray->far_) {
+                ray->far_ = scatter_distance;
+                scattered = 1;
+            }
+        }
+    }
+    int any_hit = closest_intersection(k, ray, &sf, NULL);
+    if (k->flags && !any_hit) { /* calculateTexcrd on every miss, root box or not: cuda_world.cuh:86-88 */
+        sf.u = -(0.5f + (RZ_ATAN2F(ray->direction.z, ray->direction.x) / (RZ_PI * 2.0f)));
+        sf.v = 0.5f + (RZ_ASINF(ray->direction.y) / RZ_PI);
+    }
+    if (scattered && !any_hit) { /* the medium is the surface, its normal the ray's direction (applyScattering) */
+        any_hit = 1;
+        sf.surface_material = sf.behind_material = ray->material;
+        sf.normal = sf.mapped_normal = ray->direction;
+    }
     const hiprz_material* sm = &k->s->materials[sf.surface_material];
 
-    sf.color = fetch_color(k, sm, sf.u, sf.v);
-    sf.emission = fetch_emission(k, sm, sf.u, sf.v);
+    if (k->flags & HIPRZ_COMPAT_TEXTURE_MULT) { /* opacityColor(texcrd), emission(texcrd): cuda_render_kernel.cu:158-159 */
+        sf.color = compat_opacity_color(k, sm, sf.u, sf.v);
+        sf.emission = compat_emission(k, sm, sf.u, sf.v);
+    } else if (k->flags & HIPRZ_COMPAT_FILTERING) { /* the CPU engine's fetchColor / fetchEmission, read through the texture object */
+        sf.color = sm->texture >= 0 ? compat_map(k, sm->texture, sf.u, sf.v) : col_from_u8(sm->color);
+        sf.color.a = 1.0f - sf.color.a;
+        sf.emission = sm->emission_map >= 0 ? compat_map(k, sm->emission_map, sf.u, sf.v).r : sm->emission;
+    } else {
+        sf.color = fetch_color(k, sm, sf.u, sf.v);
+        sf.emission = fetch_emission(k, sm, sf.u, sf.v);
+    }
+    if (k->flags & HIPRZ_COMPAT_BEER_LAMBERT) { /* Beer's law, cuda_render_kernel.cu:161-176: before the emission term */
+        const hiprz_material* medium = &k->s->materials[ray->material];
+        col op = col_from_u8(medium->color); /* opacityColor(), cuda_material.cuh:80-85 */
+        op.a = 1.0f - op.a;
+        ray->color = col_mul(ray->color, col_scale(op, RZ_POWF(op.a, ray->far_)));
+    }
 
     if (sf.emission > 0.0f) ts->final_color = col_add(ts->final_color, col_scale(col_mul(ray->color, sf.color), sf.emission));
 
@@ -909,8 +1191,13 @@ static tracing_result trace_ray(const kctx* k, tracing_state* ts, ray_t* ray, rn
     COUNT(k, hits, 1);
     ++ts->path_depth;
 
-    sf.metalness = fetch_metalness(k, sm, sf.u, sf.v);
-    sf.roughness = fetch_roughness(k, sm, sf.u, sf.v);
+    if (k->flags & HIPRZ_COMPAT_FILTERING) { /* metalness(texcrd) / roughness(texcrd), cuda_material.cuh:96-113 */
+        sf.metalness = sm->metalness_map >= 0 ? compat_map(k, sm->metalness_map, sf.u, sf.v).r : sm->metalness;
+        sf.roughness = sm->roughness_map >= 0 ? compat_map(k, sm->roughness_map, sf.u, sf.v).r : sm->roughness;
+    } else {
+        sf.metalness = fetch_metalness(k, sm, sf.u, sf.v);
+        sf.roughness = fetch_roughness(k, sm, sf.u, sf.v);
+    }
 
     sf.fresnel = fresnel_specular_ratio(sf.mapped_normal, ray->direction, k->s->materials[ray->material].ior,
                                         k->s->materials[sf.behind_material].ior, &sf.refr_x, &sf.refr_y);
@@ -1127,6 +1414,11 @@ static void counters_add(hiprz_counters* a, const hiprz_counters* b) {
 
 void rzo_render_pass(const hiprz_scene* scene, const hiprz_camera* camera, const hiprz_config* config,
                      rzo_context* ctx, int threads, hiprz_counters* counters) {
+    rzo_render_pass_mode(scene, camera, config, ctx, threads, counters, 0u);
+}
+
+void rzo_render_pass_mode(const hiprz_scene* scene, const hiprz_camera* camera, const hiprz_config* config,
+                          rzo_context* ctx, int threads, hiprz_counters* counters, uint32_t flags) {
     const uint32_t W = ctx->width, H = ctx->height;
     const uint32_t x_blocks = ((W - 1) / 128u) + 1, y_blocks = ((H - 1) / 128u) + 1;
     const int block_count = (int)(x_blocks * y_blocks);
@@ -1143,7 +1435,7 @@ void rzo_render_pass(const hiprz_scene* scene, const hiprz_camera* camera, const
     {
         hiprz_counters local;
         memset(&local, 0, sizeof local);
-        kctx k = {scene, camera, config, counters ? &local : NULL};
+        kctx k = {scene, camera, config, counters ? &local : NULL, flags & ~HIPRZ_COMPAT_REPROJECTION};
 #pragma omp for schedule(dynamic, 1)
         for (int b = 0; b < block_count; ++b) {
             const uint32_t by = (uint32_t)b / x_blocks, bx = (uint32_t)b % x_blocks;
@@ -1170,7 +1462,7 @@ void rzo_pick(const hiprz_scene* scene, const hiprz_camera* camera, const rzo_co
               uint32_t y, int32_t* instance_out, int32_t* material_out) {
     hiprz_config cfg;
     memset(&cfg, 0, sizeof cfg);
-    kctx k = {scene, camera, &cfg, NULL};
+    kctx k = {scene, camera, &cfg, NULL, 0u};
     ray_t ray;
     memset(&ray, 0, sizeof ray);
     generate_simple_ray(camera, &ray, x, y);

@@ -54,6 +54,13 @@ void rzo_context_reset(rzo_context* ctx); /* CameraContext::reset, cpu_engine_re
 void rzo_render_pass(const hiprz_scene* scene, const hiprz_camera* camera, const hiprz_config* config,
                      rzo_context* ctx, int threads, hiprz_counters* counters);
 
+/* The same pass with the CUDA engine's behaviours selected by HIPRZ_COMPAT_* flags (hiprz_set_mode);
+ * flags = 0 is rzo_render_pass.  HIPRZ_COMPAT_REPROJECTION is ignored: it acts on the frame at a
+ * restart, not in the integrator.  See the CUDA-compat section of rz_oracle.c for the citations and
+ * the points where it follows the HIP design instead of the CUDA text. */
+void rzo_render_pass_mode(const hiprz_scene* scene, const hiprz_camera* camera, const hiprz_config* config,
+                          rzo_context* ctx, int threads, hiprz_counters* counters, uint32_t flags);
+
 /* Kernel::rayCast (cpu_engine_kernel.cpp:102-111, 483-501). */
 void rzo_pick(const hiprz_scene* scene, const hiprz_camera* camera, const rzo_context* ctx, uint32_t x,
               uint32_t y, int32_t* instance_out, int32_t* material_out);
@@ -83,6 +90,10 @@ void rzo_cosine_sample_hemisphere(float r1, float r2, const float n[3], float ou
 void rzo_sample_sphere(float r1, float r2, const float n[3], float out[3]);
 void rzo_sample_disk(float r1, float r2, const float n[3], float radius, float out[3]);
 void rzo_tonemap_pixel(const float rgba[4], float aperture, float exposure_time, uint8_t out[4]);
+
+/* TextureBuffer::fetch of the CUDA engine (cuda_buffer.cuh:427-438) on scene->textures[texture], with its
+ * filter and address modes; *fetches (may be NULL) = texel-fetch count of the call (1) */
+void rzo_compat_fetch(const hiprz_scene* scene, int32_t texture, float u, float v, float out[4], uint64_t* fetches);
 
 const char* rzo_math_mode(void); /* "libm" or "portable" */
 

@@ -1,7 +1,9 @@
 // hiprz_compat.hpp — what the reference's CUDA engine computes and its CPU engine does not, behind
-// hiprz_set_mode().  The CPU kernel is the parity oracle, so none of this can be compared with it bit for bit: every feature has
-// its own flag, the default mode (0) never reaches this file, and the GPU tests check each feature against its analytic
-// expectation (tests/test_cuda_compat_gpu.py).
+// hiprz_set_mode().  Every feature has its own flag and the default mode (0) never reaches this file.  The CPU oracle has a compat
+// mode of its own (rzo_render_pass_mode, oracle/rz_oracle.c), restated from the CUDA text with the deliberate departures listed
+// there and in DESIGN.md: tests/test_cuda_compat_oracle_gpu.py compares this integrator with it pixel by pixel (depth, counters,
+// accumulator; libm-level agreement, not bit for bit), tests/test_cuda_compat_gpu.py checks each feature against its analytic
+// expectation.
 //
 //   HIPRZ_COMPAT_BEER_LAMBERT  ray.color *= opacityColor(medium) * pow(opacityColor(medium).alpha, distance)
 //                              (RayZath/cuda_render_kernel.cu:174-176)
@@ -20,6 +22,10 @@
 namespace hiprz {
 
 // ---- maps as CUDA texture objects sample them ----
+// texel coordinates are exact for |u * w| < 2^30; beyond that (and a NaN) they are clamped to -2^30 / +2^30 before the float -> int
+// conversion, so x0 + 1 and the address arithmetic stay inside int
+#define RZ_TEXEL_LIMIT 1073741824.0f
+RZ_DEV int compat_index(float x) { return int(floorf(fminf(fmaxf(x, -RZ_TEXEL_LIMIT), RZ_TEXEL_LIMIT))); }
 // texel index along one axis under an address mode; `inside` = false only for a border-mode access outside the image
 RZ_DEV int compat_texel(int i, int n, uint32_t mode, bool& inside) {
     inside = true;
@@ -55,11 +61,12 @@ RZ_DEV col4 compat_fetch(const DScene& s, int32_t tex, float u, float v, Counter
     RZ_COUNT(texel_fetches);
     bool in_x, in_y;
     if ((sampling & 0xFFu) != HIPRZ_TEX_FILTER_LINEAR) {
-        const int x = compat_texel(int(floorf(u * float(width))), int(width), address, in_x);
-        const int y = compat_texel(int(floorf(v * float(height))), int(height), address, in_y);
+        const int x = compat_texel(compat_index(u * float(width)), int(width), address, in_x);
+        const int y = compat_texel(compat_index(v * float(height)), int(height), address, in_y);
         return in_x && in_y ? compat_load(s, kind, offset, width, x, y) : splat(0.0f);
     }
-    const float fx = u * float(width) - 0.5f, fy = v * float(height) - 0.5f;
+    const float fx = fminf(fmaxf(u * float(width) - 0.5f, -RZ_TEXEL_LIMIT), RZ_TEXEL_LIMIT);
+    const float fy = fminf(fmaxf(v * float(height) - 0.5f, -RZ_TEXEL_LIMIT), RZ_TEXEL_LIMIT);
     const int x0 = int(floorf(fx)), y0 = int(floorf(fy));
     const float ax = fx - float(x0), ay = fy - float(y0);
     col4 sum = splat(0.0f);
@@ -101,8 +108,9 @@ RZ_DEV col4 compat_crossing_color(const DScene& s, uint32_t inst, uint32_t tri, 
     return compat_opacity_color<COUNT>(s, material, u, v, true, filtering, cnt);
 }
 
-// Shadow mask of the CUDA engine (cuda_bvh.cuh:172-232, cuda_instance.cuh:92-164, 215-229): starts white, every triangle the
-// shadow ray crosses multiplies it by that triangle's opacityColor(uv); the walk ends early once the mask's alpha drops below 1e-4.
+// Shadow mask of the CUDA engine (cuda_bvh.cuh:172-232, cuda_instance.cuh:92-164, 215-229), grouped as there: each instance forms its
+// OWN mask, the product of opacityColor(uv) over the triangles it crosses, and stops its walk once that mask's alpha drops below 1e-4;
+// the world multiplies each instance's mask into the running mask and stops once the running alpha drops below 1e-4.
 template <bool COUNT>
 RZ_DEV col4 compat_shadow_mask(const DScene& s, const Ray& ray, bool filtering, Counters& cnt) {
     col4 mask = splat(1.0f);
@@ -136,6 +144,7 @@ RZ_DEV col4 compat_shadow_mask(const DScene& s, const Ray& ray, bool filtering, 
                 const InstanceXform x = load_instance_xform(s, inst);
                 WalkRay lr;
                 to_local<false>(x, g, lr, false);
+                col4 own = splat(1.0f);
                 uint32_t m = x.blas_root;
                 while (m != RZ_END) {
                     float4 m0, m1;
@@ -155,12 +164,17 @@ RZ_DEV col4 compat_shadow_mask(const DScene& s, const Ray& ray, bool filtering, 
                             RZ_COUNT(tri_tests);
                             RZ_COUNT(shadow_tri_tests);
                             if (!tri_hit(xyz(ta), xyz(tb), xyz(tc), lr, t, b1, b2, det)) continue;
-                            mask = mask * compat_crossing_color<COUNT>(s, inst, tj, __float_as_uint(ta.w), b1, b2, filtering, cnt);
-                            if (mask.a < 1.0e-4f) return mask;
+                            own = own * compat_crossing_color<COUNT>(s, inst, tj, __float_as_uint(ta.w), b1, b2, filtering, cnt);
+                            if (own.a < 1.0e-4f) {
+                                mlink = RZ_END;
+                                break;
+                            }
                         }
                     }
                     m = mlink;
                 }
+                mask = mask * own;
+                if (mask.a < 1.0e-4f) return mask;
             }
         } else if (n == s.tlas_root) {
             return mask;  // root box missed

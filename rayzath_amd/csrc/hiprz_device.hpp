@@ -60,6 +60,7 @@ namespace hiprz {
 #define RZ_ATAN2F(y, x) atan2f(y, x)
 #define RZ_POWF(x, y) powf(x, y)
 #define RZ_EXPF(x) expf(x)
+#define RZ_LOGF(x) logf(x)
 
 // ---------------------------------------------------------------------------------------
 // Device-side views.  Every record array is addressed as float4 so a record is fetched

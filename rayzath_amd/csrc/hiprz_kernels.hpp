@@ -143,9 +143,15 @@ RZ_DEV void shade_segment(const DScene& s, const DCamera& cam, const DConfig& cf
         m = load_material(s, ray_material);
         sf.surface_material = sf.behind_material = ray_material;
         sf.normal = sf.mapped_normal = ray.d;
+        if (TEX) {  // no object found: texcrd of the sky sphere (World::closestObjectIntersection, cuda_world.cuh:86-88)
+            sf.u = -(0.5f + (RZ_ATAN2F(ray.d.z, ray.d.x) / (RZ_PI_F * 2.0f)));
+            sf.v = 0.5f + (RZ_ASINF(ray.d.y) / RZ_PI_F);
+        }
     } else {
         m = load_material(s, HIPRZ_MATERIAL_WORLD);
-        if (TEX && found == 1) {  // texcrd of the sky sphere (cpu_engine_kernel.cpp:292-295); only a map reads it
+        // texcrd of the sky sphere (cpu_engine_kernel.cpp:292-295; only a map reads it): the CPU kernel skips it when the ray misses the
+        // world's root box, the CUDA engine computes it on every miss (World::closestObjectIntersection, cuda_world.cuh:86-88)
+        if (TEX && (found == 1 || (COMPAT && found == 0))) {
             sf.u = -(0.5f + (RZ_ATAN2F(ray.d.z, ray.d.x) / (RZ_PI_F * 2.0f)));
             sf.v = 0.5f + (RZ_ASINF(ray.d.y) / RZ_PI_F);
         }
@@ -642,7 +648,7 @@ __global__ void __launch_bounds__(64, 4) rz_trace_coop_compat_kernel(const DScen
         if (sigma > 1.0e-4f) {
             const uint32_t pass = FIRST ? 0u : *f.pass, pixel_idx = p.y * cam.width + p.x;
             Rng rng(float(p.x) / float(cam.width), float(p.y) / float(cam.height), seed_value(cfg.seed, pass, (pixel_idx + ps.depth) & 255u));
-            const float distance = (-logf(rng.unsignedUniform() + 1.0e-4f)) / sigma;
+            const float distance = (-RZ_LOGF(rng.unsignedUniform() + 1.0e-4f)) / sigma;
             if (distance < ps.ray.far_) ps.ray.far_ = distance, scattered = true;
         }
     }
@@ -904,7 +910,7 @@ __global__ void __launch_bounds__(256) rz_compat_pass_kernel(const DScene s, con
         if (cfg.flags & HIPRZ_COMPAT_SCATTERING) {  // Material::applyScattering of the medium the ray travels in
             const float sigma = material_scattering(s, ps.material);
             if (sigma > 1.0e-4f) {
-                const float distance = (-logf(rng.unsignedUniform() + 1.0e-4f)) / sigma;
+                const float distance = (-RZ_LOGF(rng.unsignedUniform() + 1.0e-4f)) / sigma;
                 if (distance < ps.ray.far_) ps.ray.far_ = distance, scattered = true;
             }
         }

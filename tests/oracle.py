@@ -37,6 +37,9 @@ def load(path=LIB_PATH):
     lib.rzo_render_pass.restype = None
     lib.rzo_render_pass.argtypes = [C.POINTER(_abi.Scene), C.POINTER(_abi.Camera), C.POINTER(_abi.Config), C.POINTER(_Ctx),
                                     C.c_int, C.POINTER(_abi.Counters)]
+    lib.rzo_render_pass_mode.restype = None
+    lib.rzo_render_pass_mode.argtypes = lib.rzo_render_pass.argtypes + [U32]
+    lib.rzo_compat_fetch.restype, lib.rzo_compat_fetch.argtypes = None, [C.POINTER(_abi.Scene), C.c_int32, F, F, P, P]
     lib.rzo_pick.restype = None
     lib.rzo_pick.argtypes = [C.POINTER(_abi.Scene), C.POINTER(_abi.Camera), C.POINTER(_Ctx), U32, U32,
                              C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -56,11 +59,12 @@ def load(path=LIB_PATH):
 
 
 class OracleRenderer:
-    """CPU::Renderer + CPU::Kernel of the reference, restated (oracle/rz_oracle.c)."""
+    """CPU::Renderer + CPU::Kernel of the reference, restated (oracle/rz_oracle.c).  mode: HIPRZ_COMPAT_* flags, the CUDA engine's
+    behaviours (rzo_render_pass_mode); 0 = the CPU engine."""
 
-    def __init__(self, flat_scene, camera, config, lib=None):
+    def __init__(self, flat_scene, camera, config, lib=None, mode=0):
         self.lib = lib or load()
-        self.scene, self.camera, self.config = flat_scene, camera, config
+        self.scene, self.camera, self.config, self.mode = flat_scene, camera, config, int(mode)
         self.ctx = self.lib.rzo_context_create(camera.width, camera.height)
         self.w, self.h = camera.width, camera.height
 
@@ -82,8 +86,8 @@ class OracleRenderer:
         total = {n: 0 for n, _ in _abi.Counters._fields_}
         cnt = _abi.Counters()
         for _ in range(n_passes):
-            self.lib.rzo_render_pass(C.byref(self.scene.struct), C.byref(self.camera), C.byref(self.config), self.ctx,
-                                     threads, C.byref(cnt) if counted else None)
+            self.lib.rzo_render_pass_mode(C.byref(self.scene.struct), C.byref(self.camera), C.byref(self.config), self.ctx,
+                                          threads, C.byref(cnt) if counted else None, self.mode)
             if counted:
                 for k, v in cnt.as_dict().items():
                     total[k] += v
@@ -126,3 +130,16 @@ class OracleRenderer:
         i, m = C.c_int32(), C.c_int32()
         self.lib.rzo_pick(C.byref(self.scene.struct), C.byref(self.camera), self.ctx, x, y, C.byref(i), C.byref(m))
         return i.value, m.value
+
+
+def compat_fetch(flat_scene, texture, u, v, lib=None):
+    """TextureBuffer::fetch of the CUDA engine on flat_scene's texture `texture` at each (u, v): (..., 4) float32 and the texel-fetch count."""
+    lib = lib or load()
+    u, v = np.broadcast_arrays(np.asarray(u, np.float32), np.asarray(v, np.float32))
+    out = np.zeros(u.shape + (4,), np.float32)
+    flat_out = out.reshape(-1, 4)
+    fetches, n = C.c_uint64(), 0
+    for i, (a, b) in enumerate(zip(u.ravel(), v.ravel())):
+        lib.rzo_compat_fetch(C.byref(flat_scene.struct), texture, float(a), float(b), flat_out[i].ctypes.data, C.byref(fetches))
+        n += fetches.value
+    return out, n

@@ -1,6 +1,7 @@
-"""CUDA-compat mode (hiprz_set_mode): behaviours of the reference's CUDA engine that its CPU engine — the parity
-oracle — does not have.  They cannot be compared with the oracle, so each is checked against its ANALYTIC expectation on a scene
-built for it, next to the same scene in the default (CPU) mode:
+"""CUDA-compat mode (hiprz_set_mode): behaviours of the reference's CUDA engine that its CPU engine does not have.
+The oracle's compat mode (rzo_render_pass_mode) checks them pixel by pixel (test_cuda_compat_oracle_gpu.py; the same analytic scenes
+run in the oracle alone in test_oracle_compat.py).  Here each is checked against its ANALYTIC expectation on a scene built for it,
+next to the same scene in the default (CPU) mode:
 
   Beer-Lambert            radiance through an absorbing slab = opacityColor * alpha^thickness x the CPU-mode radiance
   medium scattering       fraction of rays scattered before a wall at distance d = 1 - exp(-sigma d) (+1e-4)
@@ -16,11 +17,11 @@ import math
 import numpy as np
 import pytest
 
+from compat_common import fog_scene, map_panel as _map_panel, sample_numpy as _sample_numpy, shadow_scene as _shadow_scene, slab_scene
 from rayzath_amd import scenes
 from rayzath_amd.engine import (COMPAT_BEER_LAMBERT, COMPAT_FILTERING, COMPAT_SCATTERING, COMPAT_SHADOW_COLOR, COMPAT_TEXTURE_MULT,
                                 Context, LightSampling, RenderConfig, Tracing)
-from rayzath_amd.scene import (Camera, Instance, Material, Mesh, SpotLight, TextureBuffer, World, camera_struct, flatten, generate_cube,
-                               generate_plane)
+from rayzath_amd.scene import Camera, TextureBuffer, camera_struct, flatten
 
 pytestmark = pytest.mark.gpu
 
@@ -36,26 +37,9 @@ def _render(world, flags, passes, max_depth, samples=(1, 1)):
     return out
 
 
-def _quad(size, z=0.0):
-    """Square [-size, size]^2 in the plane z, facing -z (towards a camera on the negative z axis), uv = ((x + size) / 2 size, (y + size) / 2 size)."""
-    v = [(-size, -size, z), (size, -size, z), (size, size, z), (-size, size, z)]
-    t = [(0, 0), (1, 0), (1, 1), (0, 1)]
-    return Mesh(v, [(0, 2, 1), (0, 3, 2)], texcrds=t, tri_texcrds=[(0, 2, 1), (0, 3, 2)], name="quad")
-
-
-def _narrow_camera(width=64, height=64, fov=0.2, z=-3.0):
-    return Camera(position=(0, 0, z), rotation=(0, 0, 0), resolution=(width, height), fov=fov, near_far=(1e-2, 1e3), focal_distance=3.0,
-                  aperture=1e-6, exposure_time=1.0 / 60.0)
-
-
 def test_beer_lambert_through_a_slab():
-    world = World()
-    glow = world.add(Material((255, 255, 255, 255), 0.0, 1.0, emission=1.0, name="panel"))
-    tinted = world.add(Material((200, 150, 100, 128), 0.0, 0.0, 0.0, 1.0, 0.0, name="absorbing glass"))   # ior 1: rays go straight through
-    world.add(Instance(world.add(_quad(3.0)), [glow], position=(0, 0, 2.0), name="panel"))
     thickness = 0.5
-    world.add(Instance(world.add(generate_cube()), [tinted], rotation=(0.0, 0.0, 0.37), scale=(4.0, 4.0, thickness), name="slab"))  # turned about z: no pixel centre on a face diagonal
-    world.camera = _narrow_camera()
+    world = slab_scene(thickness)
     # depth 3 = slab front, slab back, panel: exactly one emission term per path
     cpu, _, _ = _render(world, 0, 6, 3)
     compat, _, _ = _render(world, COMPAT_BEER_LAMBERT, 6, 3)
@@ -73,11 +57,7 @@ def test_beer_lambert_through_a_slab():
 
 def test_medium_scattering_follows_the_exponential_law():
     sigma, distance = 0.5, 4.0
-    world = World()
-    world.material = Material((255, 255, 255, 0), 0.0, 0.0, 0.0, 1.0, sigma, name="fog")
-    wall = world.add(Material((255, 255, 255, 255), 0.0, 1.0, emission=1.0, name="wall"))
-    world.add(Instance(world.add(_quad(3.0)), [wall], position=(0, 0, distance - 3.0), name="wall"))
-    world.camera = _narrow_camera(128, 128)
+    world = fog_scene(sigma, distance)
     _, depth_cpu, _ = _render(world, 0, 1, 4)
     _, depth, state = _render(world, COMPAT_SCATTERING, 1, 4)
     assert depth_cpu.min() > distance - 1e-3                          # default mode: nothing scatters (cpu_engine_kernel.cpp:539-554 is never called)
@@ -90,19 +70,6 @@ def test_medium_scattering_follows_the_exponential_law():
     trunc_mean = 1 / sigma - distance * math.exp(-sigma * distance) / (1 - math.exp(-sigma * distance))
     assert abs(free.mean() - trunc_mean) < 0.05
     assert (state["material"][depth < distance - 1e-3] == 0).all()    # a scattered ray stays in the medium
-
-
-def _shadow_scene(with_sheet):
-    world = World()
-    floor = world.add(Material((255, 255, 255, 255), 0.0, 1.0, name="floor"))
-    world.add(Instance(world.add(generate_plane(4, 8.0, 8.0)), [floor], position=(0, -1, 0), name="floor"))
-    if with_sheet:
-        sheet = world.add(Material((255, 64, 64, 128), 0.0, 0.3, name="red sheet"))
-        world.add(Instance(world.add(generate_plane(4, 1.5, 1.5)), [sheet], position=(0, 1.0, 0), name="sheet"))
-    world.add(SpotLight(position=(0, 3.0, 0), direction=(0, -1, 0), color=(255, 255, 255, 255), size=0.05, emission=200.0, beam_angle=1.2))
-    world.camera = Camera(position=(0, -0.2, -2.5), rotation=(-0.35, 0, 0), resolution=(96, 64), fov=1.0, near_far=(1e-2, 1e3),
-                          focal_distance=3.0, aperture=1e-6, exposure_time=1.0 / 60.0)
-    return world
 
 
 @pytest.mark.parametrize("shadow_walk", ["1", "0"])
@@ -121,14 +88,6 @@ def test_coloured_shadows(monkeypatch, shadow_walk):
     assert np.allclose(tinted[..., :3][lit], opaque[..., :3][lit], rtol=1e-5)  # outside the shadow nothing changes
 
 
-def _map_panel(emission_map, texture=None, color=(255, 255, 255, 255), emission=1.0):
-    world = World()
-    m = world.add(Material(color, 0.0, 1.0, emission=emission, texture=texture, emission_map=emission_map, name="panel"))
-    world.add(Instance(world.add(_quad(1.0)), [m], name="panel"))
-    world.camera = _narrow_camera(96, 96, fov=0.5)
-    return world
-
-
 def test_texture_and_emission_map_multiply():
     rng = np.random.default_rng(5)
     tex = rng.integers(30, 256, size=(8, 8, 4), dtype=np.uint8)
@@ -141,37 +100,6 @@ def test_texture_and_emission_map_multiply():
     assert on_panel.mean() > 0.3
     factor = np.array([128, 255, 64], dtype=np.float32) / np.float32(255) * np.float32(2.0)
     assert np.allclose(compat[..., :3][on_panel], cpu[..., :3][on_panel] * factor[None, :], rtol=1e-5)
-
-
-def _sample_numpy(bitmap, u, v, scale, filter_mode, address_mode):
-    """TextureBuffer::fetch of the CUDA engine on an R32F map without rotation / translation (cuda_buffer.cuh:427-438)."""
-    h, w = bitmap.shape
-    x, y = u * scale[0], 1.0 - v * scale[1]
-
-    def texel(i, n):
-        if address_mode == "clamp":
-            return np.clip(i, 0, n - 1), np.ones_like(i, dtype=bool)
-        if address_mode == "border":
-            return np.clip(i, 0, n - 1), (i >= 0) & (i < n)
-        if address_mode == "mirror":
-            k = np.mod(i, 2 * n)
-            return np.where(k < n, k, 2 * n - 1 - k), np.ones_like(i, dtype=bool)
-        return np.mod(i, n), np.ones_like(i, dtype=bool)
-
-    if filter_mode == "point":
-        xi, okx = texel(np.floor(x * w).astype(int), w)
-        yi, oky = texel(np.floor(y * h).astype(int), h)
-        return np.where(okx & oky, bitmap[yi, xi], 0.0)
-    fx, fy = x * w - 0.5, y * h - 0.5
-    x0, y0 = np.floor(fx).astype(int), np.floor(fy).astype(int)
-    ax, ay = fx - x0, fy - y0
-    out = np.zeros_like(x)
-    for k in range(4):
-        xi, okx = texel(x0 + (k & 1), w)
-        yi, oky = texel(y0 + (k >> 1), h)
-        wgt = np.where(k & 1, ax, 1 - ax) * np.where(k >> 1, ay, 1 - ay)
-        out += np.where(okx & oky, bitmap[yi, xi], 0.0) * wgt
-    return out
 
 
 @pytest.mark.parametrize("filter_mode", ["point", "linear"])
