@@ -535,6 +535,75 @@ int hiprz_read_frame(hiprz_ctx* ctx, uint32_t sequence, hiprz_frame* out);   /* 
 /* sizeof(hiprz_frame) and the offsets of ray_count and hit as this library was compiled (out[3]) */
 void hiprz_frame_layout(uint32_t out[3]);
 
+/* --- denoising: first-hit guide buffers and an edge-avoiding a-trous wavelet filter (no counterpart in the reference, whose only remedy
+ * for a noisy frame is more passes; the filter is Dammertz, Sewtz, Hanika, Lensch: "Edge-Avoiding A-Trous Wavelet Transform for fast
+ * Global Illumination Filtering", HPG 2010).  Opt-in throughout: no existing frame, readback or counter changes unless these are called.
+ *
+ * GUIDES.  One hiprz_guide per pixel, row-major, for the WHOLE frame, on the head device of the context (hiprz_set_shard, the parts of a
+ * hiprz_create_multi context and the shard mode are ignored).  rz_guide_kernel casts the pin-hole ray through the pixel centre that the
+ * first pass casts, walks to the closest hit, analyses the intersection and fetches the colour exactly as the first pass's shading does
+ * (in compat mode with the compat fetch under HIPRZ_COMPAT_FILTERING / HIPRZ_COMPAT_TEXTURE_MULT).  It draws no random numbers, writes no
+ * frame state and counts nothing.  Limitation: the guides come from the pin-hole ray — with a wide aperture they are sharper than the image.
+ * Guides belong to an accumulation: whatever restarts accumulation (camera, scene, geometry, shading, config, mode, shard, hiprz_reset)
+ * marks them stale, and hiprz_denoise renders stale guides itself. */
+typedef struct hiprz_guide {   /* 32 B, two 16-B loads */
+    float normal[3];           /* Surface::mapped_normal, world space, facing the ray; 0,0,0 on a miss */
+    float depth;               /* first-hit distance: the value hiprz_read_depth returns for the pixel */
+    float albedo[3];           /* fetchColor rgb of the first hit (texture or material colour); 1,1,1 on a miss and where the hit emits */
+    uint32_t instance;         /* index into hiprz_scene::instances, 0xFFFFFFFF on a miss */
+} hiprz_guide;
+#define HIPRZ_GUIDE_MISS 0xFFFFFFFFu
+int hiprz_render_guides(hiprz_ctx* ctx);                                  /* for the selected camera; HIPRZ_ERR_STATE before scene + camera */
+int hiprz_read_guides(hiprz_ctx* ctx, hiprz_guide* dst, size_t bytes);    /* W*H*32; renders them first when they are stale */
+/* The device buffer (W*H hiprz_guide), rendered first when stale.  The kernel that fills it may still be enqueued on the context's stream
+ * (hiprz_stream): work on another stream must wait for that stream first — hiprz_denoise_image with guides NULL does so by itself.  The
+ * pointer is valid until the camera is resized or dropped. */
+int hiprz_guides_device(hiprz_ctx* ctx, const void** out);
+
+/* THE FILTER, in fp32, deterministic (no atomics: the same bits on every run).
+ * Input: a row-major RGBA32F accumulator image as hiprz_read_accum defines it (alpha = finished paths) and W*H guides g.
+ *   radiance     r(p) = rgb(p) / (a(p) == 0 ? 1 : a(p))                                  (the tone map's own rule)
+ *   demodulation c_0(p) = r(p) / max(albedo(p), 0.01) per channel with HIPRZ_DENOISE_DEMODULATE, else c_0 = r
+ * Iteration i = 0 .. iterations - 1, step s = 2^i, taps q = p + s * (dx, dy), dx, dy in -2 .. 2, taps outside the frame skipped:
+ *   c_{i+1}(p) = sum_q w(p,q) c_i(q) / sum_q w(p,q),    w(p,q) = k(|dx|) k(|dy|) w_id w_n w_z w_c,    k = (3/8, 1/4, 1/16)   (B3 spline)
+ *   w_id = 1 when instance(p) == instance(q), else 0 (such taps are skipped)
+ *   w_n  = max(0, n_p . n_q) ^ sigma_normal;  1 between two misses
+ *   w_z  = exp(-|z_p - z_q| / (sigma_depth * z_p + 1e-6));  1 between two misses (their depth is the camera's far plane, which may be infinite)
+ *   w_c  = exp(-|t(c_i(p)) - t(c_i(q))|^2 / (sigma_color * 2^-i)^2) when sigma_color > 0, else 1, where t(c) = kc / (kc + 1) per channel
+ *          with k = pi * aperture^2 * exposure_time * 1e5 is the renderer's tone curve (the tolerance is in display units, whatever the
+ *          brightness of the scene) and |.|^2 sums the three channels; c_i is the iterate before remodulation
+ *   the centre tap (dx = dy = 0) has w_id w_n w_z w_c = 1 by definition, so the denominator never vanishes
+ *   sums run over dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), in fp32, every multiply and add rounded separately.
+ * Output: rgb = c_iterations(p) * max(albedo(p), 0.01) (with demodulation), alpha = 1: a float4 image on which the tone map yields RGBA8. */
+#define HIPRZ_DENOISE_DEMODULATE 1u
+typedef struct hiprz_denoise_params {
+    uint32_t iterations;   /* 1..6, step 2^i in iteration i */
+    float sigma_normal;    /* exponent of max(0, n_p . n_q) */
+    float sigma_depth;     /* relative depth tolerance */
+    float sigma_color;     /* colour tolerance in display units, halved every iteration; 0 = no colour term */
+    uint32_t flags;        /* HIPRZ_DENOISE_DEMODULATE (default on) */
+} hiprz_denoise_params;
+void hiprz_denoise_default_params(hiprz_denoise_params* out);
+/* Denoise the selected camera's frame: enqueues, on the context's stream, the guides when they are stale, the assembly of the row-major
+ * accumulator image (all parts of a multi-part context; summed under HIPRZ_SHARD_SAMPLES: what hiprz_read_accum returns), the filter and
+ * the tone map.  params NULL = the defaults.  HIPRZ_ERR_STATE before scene + camera upload and on a context whose hiprz_set_shard world is
+ * greater than 1 (it does not hold the frame: gather it, then hiprz_denoise_image). */
+int hiprz_denoise(hiprz_ctx* ctx, const hiprz_denoise_params* params);
+int hiprz_read_denoised(hiprz_ctx* ctx, float* rgba32f, size_t bytes);        /* W*H*16: the last hiprz_denoise of the selected camera */
+int hiprz_read_denoised_rgba8(hiprz_ctx* ctx, uint8_t* dst, size_t bytes);    /* W*H*4: its tone map */
+/* The filter as a pure function of device images (for frames gathered across processes: the place hiprz_tonemap_image_on has in that
+ * flow): accum_image_device W*H float4, guides_device W*H hiprz_guide (NULL = the context's, rendered when stale), dst W*H float4, all on
+ * the context's device; dst must not alias the input.  `stream`: a hipStream_t, NULL = the context's stream (intermediate images are the
+ * context's: one call at a time per context). */
+int hiprz_denoise_image(hiprz_ctx* ctx, const void* accum_image_device, const void* guides_device, const hiprz_denoise_params* params,
+                        void* dst_rgba32f_device, void* stream);
+/* While set (params != NULL; copied), hiprz_present puts the denoised RGBA8 into hiprz_frame.rgba8 — still only enqueueing; NULL clears
+ * it (the default).  The layout of hiprz_frame does not change.  On a context whose hiprz_set_shard world is greater than 1 hiprz_present
+ * then returns HIPRZ_ERR_STATE before it enqueues anything (no frame is presented, the sequence does not advance) until it is cleared. */
+int hiprz_set_denoise(hiprz_ctx* ctx, const hiprz_denoise_params* params);
+/* sizeof(hiprz_guide), sizeof(hiprz_denoise_params) and the offsets of hiprz_guide::albedo and ::instance as this library was compiled */
+void hiprz_denoise_layout(uint32_t out[4]);
+
 /* Device self-test of the kernels' exact-arithmetic shortcuts (shared-reciprocal division must
  * equal the correctly rounded quotient): runs 262144 * cases_per_thread random cases. */
 int hiprz_selftest(hiprz_ctx* ctx, uint32_t cases_per_thread, uint32_t seed, uint64_t* mismatches, uint64_t* tested);

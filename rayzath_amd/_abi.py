@@ -104,6 +104,21 @@ class Frame(C.Structure):  # hiprz_frame (hiprz_present / hiprz_read_frame)
                 ("passes", C.c_uint32), ("sequence", C.c_uint32), ("ray_count", C.c_uint64), ("hit", RayCast)]
 
 
+# hiprz_guide: one first-hit guide record per pixel (hiprz_read_guides)
+GUIDE_MISS = 0xFFFFFFFF
+guide_dtype = np.dtype([("normal", "<f4", 3), ("depth", "<f4"), ("albedo", "<f4", 3), ("instance", "<u4")])
+DENOISE_DEMODULATE = 1
+
+
+class Guide(C.Structure):  # hiprz_guide
+    _fields_ = [("normal", C.c_float * 3), ("depth", C.c_float), ("albedo", C.c_float * 3), ("instance", C.c_uint32)]
+
+
+class DenoiseParams(C.Structure):  # hiprz_denoise_params
+    _fields_ = [("iterations", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_color", C.c_float),
+                ("flags", C.c_uint32)]
+
+
 # name -> (restype, argtypes) of every entry point include/hiprz.h declares
 P = C.c_void_p
 U32, U64, SZ, I32 = C.c_uint32, C.c_uint64, C.c_size_t, C.c_int32
@@ -169,6 +184,16 @@ ENTRY_POINTS = {
     "hiprz_present": (C.c_int, [P, U32, U32]),
     "hiprz_read_frame": (C.c_int, [P, U32, C.POINTER(Frame)]),
     "hiprz_frame_layout": (None, [P]),
+    "hiprz_render_guides": (C.c_int, [P]),
+    "hiprz_read_guides": (C.c_int, [P, P, SZ]),
+    "hiprz_guides_device": (C.c_int, [P, C.POINTER(P)]),
+    "hiprz_denoise_default_params": (None, [C.POINTER(DenoiseParams)]),
+    "hiprz_denoise": (C.c_int, [P, C.POINTER(DenoiseParams)]),
+    "hiprz_read_denoised": (C.c_int, [P, P, SZ]),
+    "hiprz_read_denoised_rgba8": (C.c_int, [P, P, SZ]),
+    "hiprz_denoise_image": (C.c_int, [P, P, P, C.POINTER(DenoiseParams), P, P]),
+    "hiprz_set_denoise": (C.c_int, [P, C.POINTER(DenoiseParams)]),
+    "hiprz_denoise_layout": (None, [P]),
     "hiprz_selftest": (C.c_int, [P, U32, U32, C.POINTER(U64), C.POINTER(U64)]),
     "hiprz_selftest_sort": (C.c_int, [P, C.POINTER(U32), U32, C.c_int, U32, C.POINTER(U64), C.POINTER(C.c_double)]),
     "hiprz_timings": (C.c_int, [P, C.c_char_p, SZ]),

@@ -81,6 +81,10 @@ std::vector<RenderTask> prepareTasks(const std::string& task_file) {
             if (const IO::Json* v = e.find("rpp"); v && v->is_number()) t.rpp = unsigned(v->num);
             if (const IO::Json* v = e.find("timeout"); v && v->is_number()) t.timeout = float(v->num);
             if (const IO::Json* v = e.find("max depth"); v && v->is_number()) t.max_depth = unsigned(std::min(std::max(v->num, 1.0), 255.0));
+            if (const IO::Json* v = e.find("denoise")) {
+                if (!v->is_bool()) throw std::runtime_error("denoise key must be true or false");
+                t.denoise = v->b;
+            }
             return t;
         };
         std::vector<RenderTask> tasks;
@@ -162,6 +166,11 @@ std::vector<TaskResult> executeTask(const RenderTask& task, const std::string& r
         // the calls above are pipelined (sync = false): one more pass with sync = true puts the final frame into the camera
         // buffers, and the clock stops when it is there
         config.tracing.rpp = 1;
+        if (task.denoise) {  // only the frame that is kept is filtered
+            hiprz_denoise_params params;
+            hiprz_denoise_default_params(&params);
+            engine.setDenoise(&params);
+        }
         engine.renderWorld(world, config, true, true);
         result.total_traced_rays += size_t(world.camera.width) * world.camera.height * rays_per_pass_scale;
         result.duration = seconds_since(start);

@@ -20,6 +20,7 @@ struct RenderTask {  // headless.hpp:10-17
     float timeout = 60.0f;
     std::vector<std::string> engines;  // names as in Engine::engine_name + "HIPGPU"
     unsigned max_depth = 16;
+    bool denoise = false;  // "denoise": true — the saved PNG is the frame filtered with the default hiprz_denoise_params
 };
 struct TaskResult {  // headless.hpp:18-33
     std::string scene_path, engine;
@@ -29,7 +30,7 @@ struct TaskResult {  // headless.hpp:18-33
 };
 
 // Headless::prepareTasks (headless.cpp:56-160): {"tasks": {...} | [{"scene path", "engine": name | [names], "rpp", "timeout"}]};
-// relative scene paths are relative to the task file.  "max depth" is an extension (the reference renders at 16).
+// relative scene paths are relative to the task file.  "max depth" and "denoise" are extensions (the reference renders at 16 and has no filter).
 std::vector<RenderTask> prepareTasks(const std::string& task_file);
 // Headless::executeTask (headless.cpp:163-276) for the engines this host side has ("HIPGPU"; others are reported and skipped)
 std::vector<TaskResult> executeTask(const RenderTask& task, const std::string& report_dir, bool save_images, const std::vector<int>& devices, bool quiet, bool sample_sharding = true);

@@ -359,6 +359,12 @@ void Engine::shardMode(ShardMode mode) {
     m_streams_pending = false;  // the context stays as it is: the mode is about ITS parts
     check(hiprz_set_shard_mode(m_ctx, uint32_t(mode)));
 }
+void Engine::setDenoise(const hiprz_denoise_params* params) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    check(hiprz_set_denoise(m_ctx, params));
+    m_denoise = params != nullptr;
+    if (params) m_denoise_params = *params;
+}
 void Engine::tree(uint32_t tree) {
     std::lock_guard<std::mutex> lock(m_mutex);
     check(hiprz_set_tree(m_ctx, tree));
@@ -410,6 +416,7 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));
                 check(hiprz_set_tree(m_ctx, m_tree));
+                check(hiprz_set_denoise(m_ctx, m_denoise ? &m_denoise_params : nullptr));
             }
         }
     }

@@ -230,6 +230,9 @@ public:
     // wants — hiprz_headless --devices picks it.  Restarts accumulation.
     enum class ShardMode : uint32_t { Tiles = HIPRZ_SHARD_TILES, Samples = HIPRZ_SHARD_SAMPLES };
     void shardMode(ShardMode mode);
+    // hiprz_set_denoise: while set, the cameras' image buffers receive the frame filtered by the edge-avoiding a-trous filter over the
+    // first-hit guides (include/hiprz.h), for sync true and false alike; nullptr clears it (the default).  Depth buffers stay as they are.
+    void setDenoise(const hiprz_denoise_params* params);
     ~Engine();
     Engine(const Engine&) = delete;
     Engine& operator=(const Engine&) = delete;
@@ -256,6 +259,8 @@ private:
     int m_device = 0;
     bool m_streams_pending = false;  // the context is still the single one of the constructor: the first world decides
     uint32_t m_mode = 0, m_tree = HIPRZ_TREE_AUTO;  // what mode() / tree() set (the hosts' default trees: per scene), for the context that replaces it
+    bool m_denoise = false;
+    hiprz_denoise_params m_denoise_params{};
     std::mutex m_mutex;  // renderWorld is serialised (cpu_engine_core.cpp:15)
     bool m_pending_readback = false;
     struct PendingFrame {  // a frame a non-sync call presented: the next call hands it out once its own renders are enqueued

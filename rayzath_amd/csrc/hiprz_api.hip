@@ -363,6 +363,8 @@ void release_frame(hiprz_frame_state* c) {
     for (auto& t : c->sort_temp) t.keys_out.release(), t.vals_a.release(), t.vals_b.release(), t.counts.release(), t.row_total.release();
     c->shadow_keys.release(), c->shadow_perm.release();
     c->image_f4.release(), c->state_md.release(), c->state_ray.release(), c->gather.release(), c->sum_accum.release();
+    c->guides.release(), c->dn_out.release(), c->dn_rgba8.release();
+    c->guides_valid = c->dn_valid = false;
 }
 
 // Camera::reproject (cuda_camera.cuh:390-426) for one pixel of the frame that has just had its first pass: the first hit point —
@@ -444,6 +446,7 @@ int assemble_history(hiprz_ctx* c) {
         const size_t local = size_t(p->n_local_tiles) * 256u;
         if (!local) continue;
         (void)hipSetDevice(p->device);
+        if (c->gather_recorded) RZ_HIP(c, hipStreamWaitEvent(p->stream, c->gather_consumed, 0));  // an enqueued frame assembly still reads `gather`
         RZ_HIP(c, hipMemcpyPeerAsync(parts_a + stride * r, c->device, p->accum.ptr, p->device, local * sizeof(float4), p->stream));
         RZ_HIP(c, hipMemcpyPeerAsync(parts_d + stride * r, c->device, p->depth.ptr, p->device, local * sizeof(float), p->stream));
         RZ_HIP(c, hipEventRecord(p->peer_done, p->stream));
@@ -487,6 +490,7 @@ void reproject_after_first_pass(hiprz_ctx* c, const DFrame& f, const hiprz_camer
 
 int allocate_frame(hiprz_ctx* c) {
     c->frame_started = false;  // whatever history there was belongs to other buffers
+    c->guides_valid = c->dn_valid = false;
     const uint32_t W = c->camera.width, H = c->camera.height;
     c->tiles_x = (W + 31u) / 32u;
     c->tiles_y = (H + 7u) / 8u;
@@ -920,12 +924,10 @@ int render_impl(hiprz_ctx* c, uint32_t n_passes, bool counted) {
     return finish_batch(c, e0, e1, n_passes, timer);
 }
 
+// the row-major full frame of a tile-major per-pixel quantity in c->image_f4, on the context's stream: own tiles, or all parts' gathered
 template <typename T, typename PeerTiles>
-int read_untiled(hiprz_ctx* c, const T* tiles, T* dst, size_t bytes, const char* what, PeerTiles peer_tiles_of) {
-    if (!c->have_camera) return fail(c, HIPRZ_ERR_STATE, "readback before camera upload");
-    const size_t n = size_t(c->camera.width) * c->camera.height;
-    if (!dst || bytes != n * sizeof(T)) return fail(c, HIPRZ_ERR_INVALID, std::string(what) + ": destination size mismatch");
-    StageTimer timer;
+int assemble_untiled(hiprz_ctx* c, const T* tiles, PeerTiles peer_tiles_of) {
+    const size_t bytes = size_t(c->camera.width) * c->camera.height * sizeof(T);
     T* image = reinterpret_cast<T*>(c->image_f4.ptr);
     // the shards of this context cover the whole frame unless the caller split it further (hiprz_set_shard): only then are there
     // pixels nobody writes, and only then is the image cleared first
@@ -942,12 +944,16 @@ int read_untiled(hiprz_ctx* c, const T* tiles, T* dst, size_t bytes, const char*
         const size_t stride = size_t(c->n_local_tiles) * 256u;  // the head owns the lowest rank of the context: no shard has more tiles
         RZ_HIP(c, c->gather.resize(stride * n_parts * sizeof(T)));
         T* parts = reinterpret_cast<T*>(c->gather.ptr);
+        if (!c->gather_consumed) RZ_HIP(c, hipEventCreateWithFlags(&c->gather_consumed, hipEventDisableTiming));
         if (c->n_local_tiles) RZ_HIP(c, hipMemcpyAsync(parts, tiles, stride * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
         for (uint32_t r = 1; r < n_parts; ++r) {
             hiprz_ctx* p = c->peers[r - 1u];
             const size_t peer_bytes = size_t(p->n_local_tiles) * 256u * sizeof(T);
             if (!peer_bytes) continue;
             (void)hipSetDevice(p->device);
+            // the previous assembly may only be enqueued (hiprz_denoise, hiprz_present with hiprz_set_denoise): its untile kernel must have
+            // read this slice before the peer, whose stream runs ahead of the head's, overwrites it
+            if (c->gather_recorded) RZ_HIP(c, hipStreamWaitEvent(p->stream, c->gather_consumed, 0));
             RZ_HIP(c, hipMemcpyPeerAsync(parts + stride * r, c->device, peer_tiles_of(p), p->device, peer_bytes, p->stream));
             RZ_HIP(c, hipEventRecord(p->peer_done, p->stream));
             (void)hipSetDevice(c->device);
@@ -956,8 +962,19 @@ int read_untiled(hiprz_ctx* c, const T* tiles, T* dst, size_t bytes, const char*
         if (c->n_local_tiles)
             RZ_LAUNCH((rz_untile_gathered_kernel<T>), dim3(c->n_local_tiles, n_parts), dim3(256), 0, c->stream, parts, stride, image, c->camera.width,
                                c->camera.height, c->tiles_x, c->tiles_x * c->tiles_y, c->world, c->rank);
+        RZ_HIP(c, hipEventRecord(c->gather_consumed, c->stream));
+        c->gather_recorded = true;
     }
-    RZ_HIP(c, hipMemcpyAsync(dst, image, bytes, hipMemcpyDeviceToHost, c->stream));
+    return HIPRZ_OK;
+}
+template <typename T, typename PeerTiles>
+int read_untiled(hiprz_ctx* c, const T* tiles, T* dst, size_t bytes, const char* what, PeerTiles peer_tiles_of) {
+    if (!c->have_camera) return fail(c, HIPRZ_ERR_STATE, "readback before camera upload");
+    const size_t n = size_t(c->camera.width) * c->camera.height;
+    if (!dst || bytes != n * sizeof(T)) return fail(c, HIPRZ_ERR_INVALID, std::string(what) + ": destination size mismatch");
+    StageTimer timer;
+    if (const int rc = assemble_untiled<T>(c, tiles, peer_tiles_of); rc != HIPRZ_OK) return rc;
+    RZ_HIP(c, hipMemcpyAsync(dst, c->image_f4.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
     RZ_HIP(c, hipStreamSynchronize(c->stream));
     c->timings.set(what, timer.ms());
     return HIPRZ_OK;
@@ -1244,6 +1261,20 @@ int export_tiles(hiprz_ctx* c, void* dst_device, size_t bytes, const char* what,
 }
 }  // namespace
 
+namespace hiprz {
+int assemble_accum_image(hiprz_ctx* c) {
+    (void)hipSetDevice(c->device);
+    const float4* tiles = c->accum.ptr;
+    if (samples_head(c) && c->n_local_tiles) {
+        RZ_HIP(c, c->sum_accum.resize(size_t(c->n_local_tiles) * 256u));
+        const int rc = sum_parts(c, c->sum_accum.ptr);
+        if (rc != HIPRZ_OK) return rc;
+        tiles = c->sum_accum.ptr;
+    }
+    return assemble_untiled<float4>(c, tiles, [](hiprz_ctx* p) { return (const float4*)p->accum.ptr; });
+}
+}  // namespace hiprz
+
 extern "C" {
 
 int hiprz_validate_scene(const hiprz_scene* scene, char* message, size_t len) {
@@ -1421,7 +1452,9 @@ int hiprz_destroy(hiprz_ctx* c) {
     release_present(c, c);
     release_frame(c);
     c->pass_dev.release(), c->counters_dev.release(), c->pick_dev.release(), c->present_gather.release();
+    c->dn_tmp[0].release(), c->dn_tmp[1].release();
     if (c->present_consumed) (void)hipEventDestroy(c->present_consumed);
+    if (c->gather_consumed) (void)hipEventDestroy(c->gather_consumed);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1738,6 +1771,7 @@ int hiprz_upload_scene(hiprz_ctx* c, const hiprz_scene* sc) {
     c->have_scene = true;
     resolve_pipeline(c);
     c->reset_pending = true;  // world changed => accumulation restarts (cpu_engine_renderer.cpp:108-112), for every camera
+    stale_guides(c);
     for (auto& f : c->parked) f.reset_pending = true;
     c->timings.set("upload scene", timer.ms());
     return HIPRZ_OK;
@@ -1783,6 +1817,7 @@ int hiprz_update_shading(hiprz_ctx* c, const hiprz_material* materials, uint32_t
     if (!std::getenv("HIPRZ_SORT_KEY")) c->dscene.sort_variant = no_shadow_sort ? 0u : 4u;
     invalidate_graphs(c);
     c->reset_pending = true;  // the world changed: accumulation restarts (cpu_engine_renderer.cpp:108-112), for every camera
+    stale_guides(c);
     for (auto& f : c->parked) f.reset_pending = true;
     return HIPRZ_OK;
 }
@@ -1890,6 +1925,7 @@ int build_shadow_world_tree(hiprz_ctx* c, const std::vector<hiprz_instance>& din
 
 int restart_after_geometry_change(hiprz_ctx* c) {
     c->reset_pending = true;  // the world changed: accumulation restarts (cpu_engine_renderer.cpp:108-112), for every camera
+    stale_guides(c);
     for (auto& f : c->parked) f.reset_pending = true;
     return HIPRZ_OK;
 }
@@ -2058,6 +2094,7 @@ int hiprz_upload_camera(hiprz_ctx* c, const hiprz_camera* cam) {
         if (rc != HIPRZ_OK) return rc;
     }
     c->reset_pending = true;  // camera changed => context.reset (cpu_engine_renderer.cpp:108-112)
+    c->guides_valid = false;
     c->timings.set("upload camera", timer.ms());
     return HIPRZ_OK;
 }
@@ -2077,6 +2114,7 @@ int hiprz_set_config(hiprz_ctx* c, const hiprz_config* cfg) {
     // (cpu_engine_kernel.cpp:742-743, 789-790); the CUDA backend clamps to >= 1 (cuda_kernel_data.cu:23-31).
     if (cfg->spot_samples == 0 || cfg->direct_samples == 0 || cfg->spot_samples > 255u || cfg->direct_samples > 255u)
         return fail(c, HIPRZ_ERR_INVALID, "light sample counts must be 1..255");
+    if (std::memcmp(&c->config, cfg, sizeof(hiprz_config)) != 0) stale_guides(c);
     assign_setting(c, c->config, *cfg);
     return HIPRZ_OK;
 }
@@ -2086,6 +2124,7 @@ int reset_all_cameras(hiprz_ctx* c) {
     for (hiprz_ctx* p : c->peers) (void)reset_all_cameras(p);
     c->reset_pending = true;
     for (auto& f : c->parked) f.reset_pending = true;
+    stale_guides(c);
     return HIPRZ_OK;
 }
 int set_shard_one(hiprz_ctx* c, uint32_t rank, uint32_t world) {
@@ -2164,6 +2203,7 @@ int hiprz_set_mode(hiprz_ctx* c, uint32_t compat_flags) {
         const bool integrator_changed = ((compat_flags ^ c->mode_flags) & kIntegratorFlags) != 0u;
         c->mode_flags = compat_flags;
         if (integrator_changed) {
+            stale_guides(c);
             invalidate_graphs(c);
             c->reset_pending = true;  // another integrator: what has been accumulated does not mix with it
             for (auto& f : c->parked) f.reset_pending = true;
@@ -2266,6 +2306,7 @@ int hiprz_reset(hiprz_ctx* c) {
     if (!c) return HIPRZ_ERR_INVALID;
     RZ_FANOUT(c, hiprz_reset(p));
     c->reset_pending = true;
+    c->guides_valid = false;
     return HIPRZ_OK;
 }
 
@@ -2358,13 +2399,14 @@ int hiprz_read_depth(hiprz_ctx* c, float* dst, size_t bytes) {
 int hiprz_read_accum(hiprz_ctx* c, float* dst, size_t bytes) {
     if (!c) return HIPRZ_ERR_INVALID;
     (void)hipSetDevice(c->device);
-    if (samples_head(c) && c->have_camera && c->n_local_tiles) {
-        RZ_HIP(c, c->sum_accum.resize(size_t(c->n_local_tiles) * 256u));
-        const int rc = sum_parts(c, c->sum_accum.ptr);
-        if (rc != HIPRZ_OK) return rc;
-        return read_untiled<float4>(c, c->sum_accum.ptr, reinterpret_cast<float4*>(dst), bytes, "read accum", [](hiprz_ctx* p) { return (const float4*)p->accum.ptr; });
-    }
-    return read_untiled<float4>(c, c->accum.ptr, reinterpret_cast<float4*>(dst), bytes, "read accum", [](hiprz_ctx* p) { return (const float4*)p->accum.ptr; });
+    if (!c->have_camera) return fail(c, HIPRZ_ERR_STATE, "readback before camera upload");
+    if (!dst || bytes != size_t(c->camera.width) * c->camera.height * sizeof(float4)) return fail(c, HIPRZ_ERR_INVALID, "read accum: destination size mismatch");
+    StageTimer timer;
+    if (const int rc = assemble_accum_image(c); rc != HIPRZ_OK) return rc;
+    RZ_HIP(c, hipMemcpyAsync(dst, c->image_f4.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    c->timings.set("read accum", timer.ms());
+    return HIPRZ_OK;
 }
 
 int hiprz_read_state(hiprz_ctx* c, float* ray9, uint32_t* md2, size_t n_pixels) {
@@ -2545,6 +2587,9 @@ int hiprz_present(hiprz_ctx* c, uint32_t x, uint32_t y) {
     if (c->is_peer) return fail(c, HIPRZ_ERR_STATE, "present on a part of a multi-device context");
     if (!c->have_scene || !c->have_camera) return fail(c, HIPRZ_ERR_STATE, "present before scene and camera upload");
     if (!c->frame_slot[0].host || !c->copy_stream) return fail(c, HIPRZ_ERR_STATE, "present: the camera has no frame slots");
+    if (c->denoise_on && c->user_world > 1u)  // refused before anything is enqueued: the slots and the sequence stay as they are
+        return fail(c, HIPRZ_ERR_STATE, "present: hiprz_set_denoise is set, but this context renders shard " + std::to_string(c->user_rank) + " of " +
+                                            std::to_string(c->user_world) + " and does not hold the frame (clear it, or gather and hiprz_denoise_image)");
     (void)hipSetDevice(c->device);
     for (const auto& s : c->frame_slot)  // a copy of an earlier present that failed on the device
         if (s.copy_enqueued) {
@@ -2595,6 +2640,10 @@ int hiprz_present(hiprz_ctx* c, uint32_t x, uint32_t y) {
                       parts_depth, stride, rgba8, depth, W, H, c->tiles_x, n_tiles, c->world, c->rank);
         RZ_HIP(c, hipEventRecord(c->present_consumed, c->stream));
         c->consumed_recorded = true;
+    }
+    if (c->denoise_on) {  // hiprz_set_denoise: the filter's tone map replaces the slot's image (the depth stays the first-hit depth)
+        if (const int rc = denoise_frame(c, &c->denoise_params, rgba8); rc != HIPRZ_OK) return rc;
+        (void)hipSetDevice(c->device);
     }
     // the ray cast of hiprz_ray_cast: clamped pixel (camera.cpp:159-165), answered where some part of this context rendered it
     if (x >= W) x = W - 1u;

@@ -169,6 +169,14 @@ struct hiprz_frame_state {
         uint64_t ray_count = 0;
     } frame_slot[2];
     uint32_t presented = 0;  // sequence of the newest present (0: none since the camera was sized)
+    // denoising (hiprz_launch_guide.hip, hiprz_denoise.hip), head context only, allocated by the first call that needs them: the first-hit
+    // guides of the whole frame (two float4 per pixel, row-major), valid for the accumulation they were rendered in, and the last
+    // hiprz_denoise's output with its tone map
+    hiprz::DeviceArray<float4> guides;
+    bool guides_valid = false;
+    hiprz::DeviceArray<float4> dn_out;
+    hiprz::DeviceArray<uint32_t> dn_rgba8;
+    bool dn_valid = false;  // dn_out / dn_rgba8 hold a denoised frame of this camera at its current size
 };
 
 struct hiprz_ctx : hiprz_frame_state {
@@ -196,6 +204,15 @@ struct hiprz_ctx : hiprz_frame_state {
     hiprz::DeviceArray<uint8_t> present_gather;
     hipEvent_t present_consumed = nullptr;
     bool consumed_recorded = false;
+    // head, tile mode: the untile kernel of the last frame assembly has read the peers' slices of `gather` (assemble_untiled enqueues only
+    // when the denoiser calls it: a peer's next push into `gather` waits for this, the pattern of present_consumed and sum_done)
+    hipEvent_t gather_consumed = nullptr;
+    bool gather_recorded = false;
+
+    // denoising: the filter's ping-pong iterates (shared by the cameras, sized for the largest), hiprz_set_denoise
+    hiprz::DeviceArray<float4> dn_tmp[2];
+    bool denoise_on = false;
+    hiprz_denoise_params denoise_params{};
 
     // cameras (hiprz_set_camera_count / hiprz_select_camera)
     std::vector<hiprz_frame_state> parked;  // slot [active_camera] is empty while that camera's state lives in the context itself
@@ -288,6 +305,11 @@ struct hiprz_ctx : hiprz_frame_state {
 namespace hiprz {
 
 int fail(hiprz_ctx* ctx, int code, const std::string& msg);
+// accumulation restarts (or may): the guides of every camera belong to the accumulation that ends here
+inline void stale_guides(hiprz_ctx* c) {
+    c->guides_valid = false;
+    for (auto& f : c->parked) f.guides_valid = false;
+}
 
 // Every kernel instantiation a launcher can select registers its host stub at load time (RZ_LAUNCH below); hiprz_create resolves each of
 // them against the loaded code objects once per device (hipFuncGetAttributes) and refuses to come up, naming the kernel, when one is
@@ -368,6 +390,11 @@ uint32_t device_build_regions(std::vector<DeviceMesh>& meshes, uint32_t first_fr
 int device_build_mesh_trees(hiprz_ctx* c, std::vector<DeviceMesh>& meshes, const std::vector<uint32_t>& instance_mesh, bool validate);
 int device_build_world_tree(hiprz_ctx* c, bool validate);
 int device_update_triangles(hiprz_ctx* c, uint32_t first, uint32_t n, const hiprz_tri* tris, const hiprz_tri_attr* attrs);
+// the selected camera's accumulator as hiprz_read_accum defines it, assembled row-major in c->image_f4 on the context's stream (hiprz_api.hip)
+int assemble_accum_image(hiprz_ctx* c);
+// denoising: rz_guide_kernel into c->guides when they are stale (hiprz_launch_guide.hip); the filter on `stream` (hiprz_denoise.hip)
+int ensure_guides(hiprz_ctx* c);
+int denoise_frame(hiprz_ctx* c, const hiprz_denoise_params* params, uint32_t* rgba8_out);
 int sort_workspace(hiprz_ctx* c, size_t n);  // (re)allocates the sort's buffers for n keys
 int sort_temp_resize(hiprz_ctx* c, hiprz_frame_state::SortTemp& t, size_t n);
 void sort_u32(hipStream_t stream, uint32_t* keys, uint32_t n, int key_bits, uint32_t* perm, uint32_t* sorted_keys, hiprz_frame_state::SortTemp& t);  // keys destroyed

@@ -110,6 +110,23 @@ RZ_DEV int trace_path(const DScene& s, unsigned char* workspace, uint32_t* lds_c
     }
 }
 
+// fetchColor / fetchEmission (cpu_engine_kernel.cpp:505-512, 523-528) of the material `m` at the surface's texture coordinates into
+// sf.color / sf.emission.  One copy for the passes (shade_segment) and for the denoiser's guides (rz_guide_kernel), which must see the
+// colour the first pass sees.  COMPAT: the compat integrator runs (`flags` = DConfig::flags); TEX = false: the scene has no maps.
+template <bool COUNT, bool TEX, bool COMPAT>
+RZ_DEV void fetch_color_emission(const DScene& s, const Material& m, uint32_t flags, bool filtering, Surface& sf, Counters& cnt) {
+    if (COMPAT && (flags & HIPRZ_COMPAT_TEXTURE_MULT)) {  // cuda_material.cuh:86-95, 118-123: maps multiply
+        sf.color = compat_opacity_color<COUNT>(s, m, sf.u, sf.v, true, filtering, cnt);
+        sf.emission = m.emission;
+        if (m.emission_map >= 0) sf.emission *= filtering ? compat_fetch<COUNT>(s, m.emission_map, sf.u, sf.v, cnt).r : fetch_r32f<COUNT>(s, m.emission_map, sf.u, sf.v, cnt);
+    } else {
+        sf.color = from_u8(m.color);
+        if (TEX && m.texture >= 0) sf.color = filtering ? compat_fetch<COUNT>(s, m.texture, sf.u, sf.v, cnt) : fetch_rgba8<COUNT>(s, m.texture, sf.u, sf.v, cnt);
+        sf.color.a = 1.0f - sf.color.a;
+        sf.emission = TEX && m.emission_map >= 0 ? (filtering ? compat_fetch<COUNT>(s, m.emission_map, sf.u, sf.v, cnt).r : fetch_r32f<COUNT>(s, m.emission_map, sf.u, sf.v, cnt)) : m.emission;
+    }
+}
+
 // everything of traceRay after the closest hit (active lanes only): returns the segment's radiance and whether the path
 // goes on, and leaves the NEXT segment's ray / colour / material / depth in `ps` (TracingResult::repositionRay, or a fresh
 // antialiased camera ray when the path ended).  ps.ray.far_ must hold the hit distance.
@@ -157,17 +174,7 @@ RZ_DEV void shade_segment(const DScene& s, const DCamera& cam, const DConfig& cf
         }
     }
     sf.surface_scattering = m.scattering;
-    // fetchColor / fetchEmission (:505-512, 523-528)
-    if (COMPAT && (cfg.flags & HIPRZ_COMPAT_TEXTURE_MULT)) {  // cuda_material.cuh:86-95, 118-123: maps multiply
-        sf.color = compat_opacity_color<COUNT>(s, m, sf.u, sf.v, true, filtering, cnt);
-        sf.emission = m.emission;
-        if (m.emission_map >= 0) sf.emission *= filtering ? compat_fetch<COUNT>(s, m.emission_map, sf.u, sf.v, cnt).r : fetch_r32f<COUNT>(s, m.emission_map, sf.u, sf.v, cnt);
-    } else {
-        sf.color = from_u8(m.color);
-        if (TEX && m.texture >= 0) sf.color = filtering ? compat_fetch<COUNT>(s, m.texture, sf.u, sf.v, cnt) : fetch_rgba8<COUNT>(s, m.texture, sf.u, sf.v, cnt);
-        sf.color.a = 1.0f - sf.color.a;
-        sf.emission = TEX && m.emission_map >= 0 ? (filtering ? compat_fetch<COUNT>(s, m.emission_map, sf.u, sf.v, cnt).r : fetch_r32f<COUNT>(s, m.emission_map, sf.u, sf.v, cnt)) : m.emission;
-    }
+    fetch_color_emission<COUNT, TEX, COMPAT>(s, m, cfg.flags, filtering, sf, cnt);
     if (COMPAT && (cfg.flags & HIPRZ_COMPAT_BEER_LAMBERT)) {  // Beer's law in the medium the segment crossed: cuda_render_kernel.cu:158-176
         col4 medium = from_u8(load_material(s, ray_material).color);
         medium.a = 1.0f - medium.a;

@@ -43,6 +43,20 @@ TREE_REFERENCE, TREE_SAH, TREE_DEVICE, TREE_DEVICE_SAH, TREE_AUTO = range(5)   #
 SHARD_TILES, SHARD_SAMPLES = 0, 1   # hiprz_set_shard_mode
 
 
+def denoise_params(iterations=None, sigma_normal=None, sigma_depth=None, sigma_color=None, demodulate=None):
+    """hiprz_denoise_params: the library's defaults (hiprz_denoise_default_params) with the given fields replaced."""
+    p = _abi.DenoiseParams()
+    _lib.load().hiprz_denoise_default_params(C.byref(p))
+    if iterations is not None:
+        p.iterations = int(iterations)
+    for name, value in (("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth), ("sigma_color", sigma_color)):
+        if value is not None:
+            setattr(p, name, float(value))
+    if demodulate is not None:
+        p.flags = (p.flags & ~_abi.DENOISE_DEMODULATE) | (_abi.DENOISE_DEMODULATE if demodulate else 0)
+    return p
+
+
 def default_streams(n_lights):
     """How many contexts-with-a-stream the hosts put on ONE GPU (hiprz_create_multi with the device named that often, tiles interleaved):
     two when the scene has no lights — one half's sorts, pass bookkeeping and kernel tails run beside the other half's walks (measured on
@@ -304,6 +318,47 @@ class Context:
         return dict(rgba8=rgba8, depth=depth, width=w, height=h, passes=f.passes, sequence=f.sequence, ray_count=f.ray_count,
                     hit=(f.hit.instance, f.hit.material_slot, f.hit.material, f.hit.triangle))
 
+    # --- denoising: first-hit guides and the a-trous filter (include/hiprz.h) ---
+    @staticmethod
+    def _params(params):
+        return None if params is None else C.byref(params)
+
+    def render_guides(self):
+        self._check(self.lib.hiprz_render_guides(self._ctx))
+
+    def read_guides(self):
+        """(H, W) array of _abi.guide_dtype: normal, depth, albedo, instance of every pixel's first hit (rendered when stale)."""
+        out = np.zeros((self.height, self.width), dtype=_abi.guide_dtype)
+        self._check(self.lib.hiprz_read_guides(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def guides_device(self):
+        v = C.c_void_p()
+        self._check(self.lib.hiprz_guides_device(self._ctx, C.byref(v)))
+        return v.value
+
+    def denoise(self, params=None):
+        """hiprz_denoise: guides (when stale), assembly, filter and tone map of the selected camera's frame, enqueued; None = the defaults."""
+        self._check(self.lib.hiprz_denoise(self._ctx, self._params(params)))
+
+    def read_denoised(self):
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        self._check(self.lib.hiprz_read_denoised(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def read_denoised_rgba8(self):
+        out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        self._check(self.lib.hiprz_read_denoised_rgba8(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def denoise_image(self, accum_ptr, guides_ptr, params, dst_ptr, stream=None):
+        """The filter on device images: W*H float4 accumulator, W*H guides (None = the context's), W*H float4 destination."""
+        self._check(self.lib.hiprz_denoise_image(self._ctx, accum_ptr, guides_ptr, self._params(params), dst_ptr, stream))
+
+    def set_denoise(self, params):
+        """While set (params not None), present() delivers the denoised image in the frame's rgba8; None clears it."""
+        self._check(self.lib.hiprz_set_denoise(self._ctx, self._params(params)))
+
     def selftest(self, cases_per_thread=64, seed=1):
         bad, n = C.c_uint64(), C.c_uint64()
         self._check(self.lib.hiprz_selftest(self._ctx, cases_per_thread, seed, C.byref(bad), C.byref(n)))
@@ -380,12 +435,14 @@ class Engine:
 
     REBUILD_EVERY = 16   # moved frames (World.mark_moved) between two device rebuilds of the refitted trees
 
-    def __init__(self, device=0, streams=None, pipelined=False):
+    def __init__(self, device=0, streams=None, pipelined=False, denoise=None):
         """`device`: a GPU id, or a list of ids (one context over several GPUs).  `streams` (single GPU only): how many contexts share
         the GPU, None = default_streams() of the first world rendered; asking for `engine.context` before that settles for one.
         `pipelined`: frames leave through Context.present / read_frame, and renderWorld(sync=False) hands out the PREVIOUS call's frame
-        while this call's renders (the C++ engine's sync=false); the default reads every frame synchronously and ignores `sync`."""
+        while this call's renders (the C++ engine's sync=false); the default reads every frame synchronously and ignores `sync`.
+        `denoise`: None, or _abi.DenoiseParams (denoise_params()): the cameras' image buffers receive the denoised frame, on both paths."""
         self._device, self._streams, self._context = device, streams, None
+        self._denoise = denoise
         self._pipelined = pipelined
         self._pending = []  # pipelined, sync=False: (camera slot, camera, sequence) presented by the previous call, not yet handed out
         self._tree = TREE_AUTO   # the hosts' default: the snapshot's trees for scenes staged in LDS, the device's surface-area trees otherwise
@@ -398,7 +455,14 @@ class Engine:
         if self._context is None:
             self._context = Context(self._device)
             self._context.set_tree(self._tree)
+            self._context.set_denoise(self._denoise)
         return self._context
+
+    def set_denoise(self, params):
+        """None, or the parameters of the filter whose output the cameras' image buffers receive from the next frame on."""
+        self._denoise = params
+        if self._context is not None:
+            self._context.set_denoise(params)
 
     def set_tree(self, tree):
         """Context.set_tree for the engine's context (default TREE_AUTO); takes effect at the next scene upload, which this forces."""
@@ -418,6 +482,7 @@ class Engine:
             k = self._streams or default_streams(len(world.spot_lights) + len(world.direct_lights))
             self._context = Context([self._device] * k) if k > 1 else Context(self._device)
             self._context.set_tree(self._tree)
+            self._context.set_denoise(self._denoise)
             if getattr(self, "_mode", 0):
                 self._context.set_mode(self._mode)
         ctx = self.context
@@ -481,8 +546,12 @@ class Engine:
                 else:
                     self._pending.append((k, cam, seq))
                 continue
-            ctx.tonemap()
-            cam.image_buffer = ctx.read_rgba8()  # synchronises
+            if self._denoise is not None:
+                ctx.denoise(self._denoise)
+                cam.image_buffer = ctx.read_denoised_rgba8()  # synchronises
+            else:
+                ctx.tonemap()
+                cam.image_buffer = ctx.read_rgba8()  # synchronises
             cam.depth_buffer = ctx.read_depth()
             cam.ray_count = ctx.ray_count()
             # Kernel::rayCast after every frame (cpu_engine_renderer.cpp:176): what the camera's ray-cast pixel looks at
