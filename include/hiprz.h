@@ -574,20 +574,40 @@ int hiprz_guides_device(hiprz_ctx* ctx, const void** out);
  *          brightness of the scene) and |.|^2 sums the three channels; c_i is the iterate before remodulation
  *   the centre tap (dx = dy = 0) has w_id w_n w_z w_c = 1 by definition, so the denominator never vanishes
  *   sums run over dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), in fp32, every multiply and add rounded separately.
- * Output: rgb = c_iterations(p) * max(albedo(p), 0.01) (with demodulation), alpha = 1: a float4 image on which the tone map yields RGBA8. */
+ * Output: rgb = c_iterations(p) * max(albedo(p), 0.01) (with demodulation), alpha = 1: a float4 image on which the tone map yields RGBA8.
+ *
+ * THE VARIANCE-GUIDED FILTER (HIPRZ_DENOISE_VARIANCE, after Schied et al.: "Spatiotemporal Variance-Guided Filtering", HPG 2017): the
+ * luminance tolerance of a tap is a multiple of the local standard deviation of the estimate (VARIANCE below), and the variance is
+ * carried through the iterations.  Everything not restated here is as above: w_id, w_n, w_z, the spline, the tap order, the centre tap,
+ * demodulation, output.  V(p) = (V_r, V_g, V_b, K) is the W*H image hiprz_read_variance defines.
+ *   lum(c) = (0.2126 c_r + 0.7152 c_g) + 0.0722 c_b
+ *   v_0(p) = lum(sd)^2 with sd_ch = sqrt(V_ch(p)) / a_ch(p), a_ch = max(albedo_ch(p), 0.01) with demodulation, else 1;
+ *            v_0(p) = -1 ("no estimate") where K(p) < 2.  The channels' standard deviations are added, not their variances: the noise of
+ *            a pixel's channels is almost perfectly correlated, and this is the upper bound.
+ *   iteration i, step s = 2^i, the same 25 taps q:
+ *   g_i(p)     = sum_q k(|dx|) k(|dy|) v_i(q) / sum_q k(|dx|) k(|dy|) over the taps in the frame, of p's instance, with v_i(q) >= 0 (the
+ *                centre among them, in the tap order)
+ *   w_l(p,q)   = exp(-|lum(c_i(p)) - lum(c_i(q))| / (sigma_color * sqrt(g_i(p)) + 1e-10));  1 when v_i(p) < 0;  it replaces w_c, and
+ *                sigma_color is in standard deviations here (SVGF uses 4), not halved per iteration
+ *   c_{i+1}(p) = sum_q w c_i(q) / sum_q w  as before, w = k k w_id w_n w_z w_l
+ *   v_{i+1}(p) = sum_q w^2 max(v_i(q), 0) / (sum_q w)^2 over the same taps;  -1 when v_i(p) < 0
+ * A pixel without an estimate (K < 2) is filtered by the guides alone (w_l = 1) and hands no variance on. */
 #define HIPRZ_DENOISE_DEMODULATE 1u
+#define HIPRZ_DENOISE_VARIANCE 2u   /* the variance-guided filter: needs hiprz_set_variance (hiprz_denoise) or a variance image (hiprz_denoise_image_variance) */
 typedef struct hiprz_denoise_params {
     uint32_t iterations;   /* 1..6, step 2^i in iteration i */
     float sigma_normal;    /* exponent of max(0, n_p . n_q) */
     float sigma_depth;     /* relative depth tolerance */
-    float sigma_color;     /* colour tolerance in display units, halved every iteration; 0 = no colour term */
-    uint32_t flags;        /* HIPRZ_DENOISE_DEMODULATE (default on) */
+    float sigma_color;     /* colour tolerance in display units, halved every iteration; 0 = no colour term.  Under HIPRZ_DENOISE_VARIANCE:
+                              the luminance tolerance in standard deviations, the same in every iteration */
+    uint32_t flags;        /* HIPRZ_DENOISE_DEMODULATE (default on) | HIPRZ_DENOISE_VARIANCE (default off) */
 } hiprz_denoise_params;
 void hiprz_denoise_default_params(hiprz_denoise_params* out);
 /* Denoise the selected camera's frame: enqueues, on the context's stream, the guides when they are stale, the assembly of the row-major
  * accumulator image (all parts of a multi-part context; summed under HIPRZ_SHARD_SAMPLES: what hiprz_read_accum returns), the filter and
  * the tone map.  params NULL = the defaults.  HIPRZ_ERR_STATE before scene + camera upload and on a context whose hiprz_set_shard world is
- * greater than 1 (it does not hold the frame: gather it, then hiprz_denoise_image). */
+ * greater than 1 (it does not hold the frame: gather it, then hiprz_denoise_image).  With HIPRZ_DENOISE_VARIANCE the filter takes the
+ * context's variance image (hiprz_variance_device): HIPRZ_ERR_STATE while hiprz_set_variance is off. */
 int hiprz_denoise(hiprz_ctx* ctx, const hiprz_denoise_params* params);
 int hiprz_read_denoised(hiprz_ctx* ctx, float* rgba32f, size_t bytes);        /* W*H*16: the last hiprz_denoise of the selected camera */
 int hiprz_read_denoised_rgba8(hiprz_ctx* ctx, uint8_t* dst, size_t bytes);    /* W*H*4: its tone map */
@@ -597,12 +617,49 @@ int hiprz_read_denoised_rgba8(hiprz_ctx* ctx, uint8_t* dst, size_t bytes);    /*
  * context's: one call at a time per context). */
 int hiprz_denoise_image(hiprz_ctx* ctx, const void* accum_image_device, const void* guides_device, const hiprz_denoise_params* params,
                         void* dst_rgba32f_device, void* stream);
+/* The same for the variance-guided filter: variance_image_device is a W*H float4 image (V_r, V_g, V_b, K) as hiprz_read_variance defines
+ * it.  HIPRZ_ERR_INVALID when params do not carry HIPRZ_DENOISE_VARIANCE or the variance image is NULL or aliases dst; plain
+ * hiprz_denoise_image returns HIPRZ_ERR_INVALID for params that carry the flag. */
+int hiprz_denoise_image_variance(hiprz_ctx* ctx, const void* accum_image_device, const void* guides_device, const void* variance_image_device,
+                                 const hiprz_denoise_params* params, void* dst_rgba32f_device, void* stream);
 /* While set (params != NULL; copied), hiprz_present puts the denoised RGBA8 into hiprz_frame.rgba8 — still only enqueueing; NULL clears
  * it (the default).  The layout of hiprz_frame does not change.  On a context whose hiprz_set_shard world is greater than 1 hiprz_present
  * then returns HIPRZ_ERR_STATE before it enqueues anything (no frame is presented, the sequence does not advance) until it is cleared. */
 int hiprz_set_denoise(hiprz_ctx* ctx, const hiprz_denoise_params* params);
 /* sizeof(hiprz_guide), sizeof(hiprz_denoise_params) and the offsets of hiprz_guide::albedo and ::instance as this library was compiled */
 void hiprz_denoise_layout(uint32_t out[4]);
+
+/* --- VARIANCE: a per-pixel estimate of the variance of the frame's mean radiance, from batch moments of the accumulator (no counterpart
+ * in the reference).  Opt-in: while off (the default) nothing is allocated and no frame, readback, counter, graph capture or timing changes;
+ * no render kernel changes either way.  A real change of the value restarts accumulation, as hiprz_set_mode does.
+ *
+ * THE BATCHES are the caller's: one per hiprz_render / hiprz_render_counted call (the Engine hosts render one call per frame: one batch
+ * per frame).  Behind the passes of every call rz_moments_kernel compares, per pixel, the accumulator with its value when the pixel's
+ * last batch closed, d = accum - snap (four components), in fp32, every operation rounded separately, deterministic:
+ *   d.w >= 1:  S2_ch += d_ch * d_ch;  S1_ch += d_ch * d.w;  SA += d.w * d.w;  K += 1;  snap = accum       (the batch closes for this pixel)
+ *   else nothing is written: the accumulator gains radiance in every path segment but alpha only when a path finishes, so a batch in
+ *   which no path finished is a fragment of a sample and merges into the next one.
+ * A call that restarts the frame zeroes snap, the sums and K first; when it carries history over (HIPRZ_COMPAT_REPROJECTION) it only
+ * sets snap = accum — the blended history is not a sample.  A single hiprz_render(64) therefore yields K = 1 and no estimate: render the
+ * passes in several calls.
+ *
+ * THE ESTIMATE, per pixel and channel, with R, A the accumulator as hiprz_read_accum returns it: V is the variance of the mean radiance
+ * r = R / A that the tone map shows — the linearised ratio-estimator variance over the K closed batches (R_k, A_k):
+ *   K < 2:  (0, 0, 0, K)
+ *   E    = max(0, (S2_ch - (2 r) S1_ch) + (r r) SA)            = sum_k (R_k - r A_k)^2
+ *   V_ch = (E (K / (K - 1))) / (A A)
+ * It is coarse at low K (its own relative error is about sqrt(2 / (K - 1))), 0 where fewer than two batches have closed, and biased
+ * upwards when paths straddle batches and collect light along the way (next-event estimation): the fragment lands in one batch and the
+ * alpha in the next.  Multi-part contexts: under HIPRZ_SHARD_TILES every pixel's moments live on the part that owns it and the image is
+ * assembled as the accumulator's is; under HIPRZ_SHARD_SAMPLES the parts' batches are just more batches — the sums and K are added over
+ * the parts in part order and the formula runs on the summed accumulator.  Pixels this context does not own (hiprz_set_shard) read as 0.
+ * Out of scope: exporting the moments as tiles for frames sharded over several processes (hiprz_set_shard world > 1). */
+int hiprz_set_variance(hiprz_ctx* ctx, int enabled);                      /* default 0; fans out to the parts of a multi-part context */
+/* W*H*16 bytes, row-major: (V_r, V_g, V_b, K) per pixel of the selected camera.  HIPRZ_ERR_STATE while variance is off or before scene and
+ * camera upload, HIPRZ_ERR_INVALID on a size mismatch. */
+int hiprz_read_variance(hiprz_ctx* ctx, float* dst, size_t bytes);
+/* The same image on the head device, enqueued on the context's stream: the contract of hiprz_guides_device. */
+int hiprz_variance_device(hiprz_ctx* ctx, const void** out);
 
 /* Device self-test of the kernels' exact-arithmetic shortcuts (shared-reciprocal division must
  * equal the correctly rounded quotient): runs 262144 * cases_per_thread random cases. */

@@ -108,6 +108,7 @@ class Frame(C.Structure):  # hiprz_frame (hiprz_present / hiprz_read_frame)
 GUIDE_MISS = 0xFFFFFFFF
 guide_dtype = np.dtype([("normal", "<f4", 3), ("depth", "<f4"), ("albedo", "<f4", 3), ("instance", "<u4")])
 DENOISE_DEMODULATE = 1
+DENOISE_VARIANCE = 2  # the variance-guided filter (hiprz_set_variance's estimate, or hiprz_denoise_image_variance's image)
 
 
 class Guide(C.Structure):  # hiprz_guide
@@ -192,7 +193,11 @@ ENTRY_POINTS = {
     "hiprz_read_denoised": (C.c_int, [P, P, SZ]),
     "hiprz_read_denoised_rgba8": (C.c_int, [P, P, SZ]),
     "hiprz_denoise_image": (C.c_int, [P, P, P, C.POINTER(DenoiseParams), P, P]),
+    "hiprz_denoise_image_variance": (C.c_int, [P, P, P, P, C.POINTER(DenoiseParams), P, P]),
     "hiprz_set_denoise": (C.c_int, [P, C.POINTER(DenoiseParams)]),
+    "hiprz_set_variance": (C.c_int, [P, C.c_int]),
+    "hiprz_read_variance": (C.c_int, [P, P, SZ]),
+    "hiprz_variance_device": (C.c_int, [P, C.POINTER(P)]),
     "hiprz_denoise_layout": (None, [P]),
     "hiprz_selftest": (C.c_int, [P, U32, U32, C.POINTER(U64), C.POINTER(U64)]),
     "hiprz_selftest_sort": (C.c_int, [P, C.POINTER(U32), U32, C.c_int, U32, C.POINTER(U64), C.POINTER(C.c_double)]),

@@ -82,8 +82,9 @@ std::vector<RenderTask> prepareTasks(const std::string& task_file) {
             if (const IO::Json* v = e.find("timeout"); v && v->is_number()) t.timeout = float(v->num);
             if (const IO::Json* v = e.find("max depth"); v && v->is_number()) t.max_depth = unsigned(std::min(std::max(v->num, 1.0), 255.0));
             if (const IO::Json* v = e.find("denoise")) {
-                if (!v->is_bool()) throw std::runtime_error("denoise key must be true or false");
-                t.denoise = v->b;
+                if (v->is_string() && v->str == "variance") t.denoise = t.denoise_variance = true;
+                else if (!v->is_bool()) throw std::runtime_error("denoise key must be true, false or \"variance\"");
+                else t.denoise = v->b;
             }
             return t;
         };
@@ -129,6 +130,12 @@ std::vector<TaskResult> executeTask(const RenderTask& task, const std::string& r
 
         // Headless::render (headless.cpp:277-296): one pipelined renderWorld, then steer the passes per call so that a call
         // takes `load_time` (the square root damps the correction, the running mean damps it again)
+        if (task.denoise_variance) {  // the estimate needs every call of the task as a batch: on from the first one
+            hiprz_denoise_params params;
+            hiprz_denoise_default_params(&params);
+            params.flags |= HIPRZ_DENOISE_VARIANCE, params.sigma_color = 4.0f;
+            engine.setDenoise(&params);
+        }
         const float load_time = 0.1f;
         float floaty_rpp = 1.0f;
         auto render = [&]() {
@@ -166,7 +173,7 @@ std::vector<TaskResult> executeTask(const RenderTask& task, const std::string& r
         // the calls above are pipelined (sync = false): one more pass with sync = true puts the final frame into the camera
         // buffers, and the clock stops when it is there
         config.tracing.rpp = 1;
-        if (task.denoise) {  // only the frame that is kept is filtered
+        if (task.denoise && !task.denoise_variance) {  // only the frame that is kept is filtered
             hiprz_denoise_params params;
             hiprz_denoise_default_params(&params);
             engine.setDenoise(&params);

@@ -21,6 +21,7 @@ struct RenderTask {  // headless.hpp:10-17
     std::vector<std::string> engines;  // names as in Engine::engine_name + "HIPGPU"
     unsigned max_depth = 16;
     bool denoise = false;  // "denoise": true — the saved PNG is the frame filtered with the default hiprz_denoise_params
+    bool denoise_variance = false;  // "denoise": "variance" — ... with the variance-guided filter at sigma_color 4; every render call of the task is a batch
 };
 struct TaskResult {  // headless.hpp:18-33
     std::string scene_path, engine;

@@ -361,6 +361,8 @@ void Engine::shardMode(ShardMode mode) {
 }
 void Engine::setDenoise(const hiprz_denoise_params* params) {
     std::lock_guard<std::mutex> lock(m_mutex);
+    // the context's variance estimate is on exactly while the parameters ask for the variance-guided filter (a change restarts accumulation)
+    check(hiprz_set_variance(m_ctx, params && (params->flags & HIPRZ_DENOISE_VARIANCE) ? 1 : 0));
     check(hiprz_set_denoise(m_ctx, params));
     m_denoise = params != nullptr;
     if (params) m_denoise_params = *params;
@@ -416,6 +418,7 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));
                 check(hiprz_set_tree(m_ctx, m_tree));
+                check(hiprz_set_variance(m_ctx, m_denoise && (m_denoise_params.flags & HIPRZ_DENOISE_VARIANCE) ? 1 : 0));
                 check(hiprz_set_denoise(m_ctx, m_denoise ? &m_denoise_params : nullptr));
             }
         }

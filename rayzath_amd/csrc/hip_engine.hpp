@@ -232,6 +232,8 @@ public:
     void shardMode(ShardMode mode);
     // hiprz_set_denoise: while set, the cameras' image buffers receive the frame filtered by the edge-avoiding a-trous filter over the
     // first-hit guides (include/hiprz.h), for sync true and false alike; nullptr clears it (the default).  Depth buffers stay as they are.
+    // Parameters with HIPRZ_DENOISE_VARIANCE also switch the context's variance estimate on (hiprz_set_variance; every renderWorld call is
+    // one batch), any others switch it off: a change of that restarts accumulation.
     void setDenoise(const hiprz_denoise_params* params);
     ~Engine();
     Engine(const Engine&) = delete;

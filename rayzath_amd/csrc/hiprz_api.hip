@@ -66,6 +66,41 @@ __global__ void __launch_bounds__(256) rz_sum_parts_kernel(const float4* own, co
     out[i] = a;
 }
 
+// hiprz_set_variance (include/hiprz.h "VARIANCE"): one thread per local pixel behind the passes of a render call.  The call's batch closes
+// for a pixel when at least one path finished in it since the pixel's last closed batch (the accumulator gains radiance in every segment,
+// alpha only when a path ends: a batch without a finished path is a fragment of a sample and merges into the next one).  snap_only: the
+// call restarted the frame from reprojected history, which is no sample.
+__global__ void __launch_bounds__(256) rz_moments_kernel(const float4* accum, float4* snap, float4* m0, float4* m1, uint32_t n, uint32_t snap_only) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = accum[i];
+    if (snap_only) {
+        snap[i] = a;
+        return;
+    }
+    const float4 s = snap[i];
+    const float dr = a.x - s.x, dg = a.y - s.y, db = a.z - s.z, dw = a.w - s.w;
+    if (!(dw >= 1.0f)) return;
+    float4 u = m0[i], v = m1[i];
+    u.x = u.x + dr * dr, u.y = u.y + dg * dg, u.z = u.z + db * db, u.w = u.w + dw * dw;
+    v.x = v.x + dr * dw, v.y = v.y + dg * dw, v.z = v.z + db * dw, v.w = v.w + 1.0f;
+    m0[i] = u, m1[i] = v, snap[i] = a;
+}
+// the estimate of hiprz_read_variance from the accumulator and the moments, per local pixel
+RZ_DEV float variance_of(float R, float A, float S2, float S1, float SA, float K) {
+    const float r = R / A;
+    const float E = fmaxf(0.0f, (S2 - (2.0f * r) * S1) + (r * r) * SA);
+    return (E * (K / (K - 1.0f))) / (A * A);
+}
+__global__ void __launch_bounds__(256) rz_variance_kernel(const float4* accum, const float4* m0, const float4* m1, float4* out, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = accum[i], u = m0[i], v = m1[i];
+    float4 o = make_float4(0.0f, 0.0f, 0.0f, v.w);
+    if (v.w >= 2.0f) o.x = variance_of(a.x, a.w, u.x, v.x, u.w, v.w), o.y = variance_of(a.y, a.w, u.y, v.y, u.w, v.w), o.z = variance_of(a.z, a.w, u.z, v.z, u.w, v.w);
+    out[i] = o;
+}
+
 // tile-major (owned tiles of shard rank/world) -> row-major full frame
 template <typename T>
 __global__ void __launch_bounds__(256) rz_untile_kernel(const T* tiles, T* image, uint32_t width, uint32_t height,
@@ -353,6 +388,9 @@ struct TreeCheck {
     }
 };
 
+void release_variance(hiprz_frame_state* c) {
+    c->var_snap.release(), c->var_m0.release(), c->var_m1.release(), c->var_tiles.release(), c->var_image.release(), c->sum_m0.release(), c->sum_m1.release();
+}
 void release_frame(hiprz_frame_state* c) {
     c->st0.release(), c->st1.release(), c->st2.release(), c->accum.release(), c->depth.release(), c->rgba8.release();
     c->hit0.release(), c->hit1.release();
@@ -365,6 +403,7 @@ void release_frame(hiprz_frame_state* c) {
     c->image_f4.release(), c->state_md.release(), c->state_ray.release(), c->gather.release(), c->sum_accum.release();
     c->guides.release(), c->dn_out.release(), c->dn_rgba8.release();
     c->guides_valid = c->dn_valid = false;
+    release_variance(c);
 }
 
 // Camera::reproject (cuda_camera.cuh:390-426) for one pixel of the frame that has just had its first pass: the first hit point —
@@ -804,7 +843,7 @@ std::vector<unsigned char> graph_key_of(hiprz_ctx* c, const DFrame& f, uint32_t 
     return key;
 }
 
-int render_impl(hiprz_ctx* c, uint32_t n_passes, bool counted) {
+int render_passes(hiprz_ctx* c, uint32_t n_passes, bool counted) {
     if (!c->have_scene || !c->have_camera) return fail(c, HIPRZ_ERR_STATE, "render before scene and camera upload");
     if (n_passes == 0 || c->n_local_tiles == 0) return HIPRZ_OK;
     resolve_pipeline(c);  // the choice depends on the selected camera's shard size too
@@ -924,11 +963,41 @@ int render_impl(hiprz_ctx* c, uint32_t n_passes, bool counted) {
     return finish_batch(c, e0, e1, n_passes, timer);
 }
 
+// A render call: its passes and, under hiprz_set_variance, the batch they form — the moments are zeroed before the passes of a call that
+// restarts the frame, and rz_moments_kernel follows the passes eagerly on the same stream (behind the graph launch or the resident
+// kernel: it is no part of the captured graph, and nothing the graph's key holds depends on it).
+int render_impl(hiprz_ctx* c, uint32_t n_passes, bool counted) {
+    const bool batch = c->variance_on && c->have_scene && c->have_camera && n_passes != 0u && c->n_local_tiles != 0u;
+    const size_t n = size_t(c->n_local_tiles) * 256u;
+    bool snap_only = false;
+    if (batch) {
+        // (a buffer that had to be allocated is zeroed too: hiprz_set_variance and whatever sizes a frame leave a restart pending)
+        const bool fresh = c->reset_pending || c->var_snap.count < n || c->var_m0.count < n || c->var_m1.count < n;
+        RZ_HIP(c, c->var_snap.resize(n));
+        RZ_HIP(c, c->var_m0.resize(n));
+        RZ_HIP(c, c->var_m1.resize(n));
+        if (fresh) {
+            RZ_HIP(c, hipMemsetAsync(c->var_snap.ptr, 0, n * sizeof(float4), c->stream));
+            RZ_HIP(c, hipMemsetAsync(c->var_m0.ptr, 0, n * sizeof(float4), c->stream));
+            RZ_HIP(c, hipMemsetAsync(c->var_m1.ptr, 0, n * sizeof(float4), c->stream));
+        }
+        // keep_history's own condition: the first pass of this call is followed by the reprojection of the previous frame
+        snap_only = c->reset_pending && (c->mode_flags & HIPRZ_COMPAT_REPROJECTION) && c->frame_started;
+    }
+    const int rc = render_passes(c, n_passes, counted);
+    if (rc != HIPRZ_OK || !batch) return rc;
+    RZ_LAUNCH(rz_moments_kernel, dim3(c->n_local_tiles), dim3(256), 0, c->stream, c->accum.ptr, c->var_snap.ptr, c->var_m0.ptr, c->var_m1.ptr, uint32_t(n),
+              snap_only ? 1u : 0u);
+    RZ_HIP(c, hipGetLastError());
+    return HIPRZ_OK;
+}
+
 // the row-major full frame of a tile-major per-pixel quantity in c->image_f4, on the context's stream: own tiles, or all parts' gathered
+// (or in `image`: the variance estimate has staging of its own, image_f4 holds the accumulator image the filter reads beside it)
 template <typename T, typename PeerTiles>
-int assemble_untiled(hiprz_ctx* c, const T* tiles, PeerTiles peer_tiles_of) {
+int assemble_untiled(hiprz_ctx* c, const T* tiles, PeerTiles peer_tiles_of, T* image = nullptr) {
     const size_t bytes = size_t(c->camera.width) * c->camera.height * sizeof(T);
-    T* image = reinterpret_cast<T*>(c->image_f4.ptr);
+    if (!image) image = reinterpret_cast<T*>(c->image_f4.ptr);
     // the shards of this context cover the whole frame unless the caller split it further (hiprz_set_shard): only then are there
     // pixels nobody writes, and only then is the image cleared first
     if (c->user_world > 1u) RZ_HIP(c, hipMemsetAsync(image, 0, bytes, c->stream));
@@ -1208,7 +1277,8 @@ bool samples_head(const hiprz_ctx* c) { return c->shard_mode == HIPRZ_SHARD_SAMP
 // Every peer pushes its accumulators into its slice of the head's staging buffer on ITS stream, behind its own rendering (peer-to-peer
 // over xGMI for another device), the head's stream waits for all of them and one launch adds them up in part order.  A peer's next push
 // waits for that launch (sum_done): nothing here synchronises with the host.
-int sum_parts(hiprz_ctx* c, float4* out) {
+template <typename Buffer>
+int sum_parts_of(hiprz_ctx* c, float4* out, Buffer buffer_of) {
     const size_t n = size_t(c->n_local_tiles) * 256u;
     if (!n) return HIPRZ_OK;
     (void)hipSetDevice(c->device);
@@ -1218,19 +1288,22 @@ int sum_parts(hiprz_ctx* c, float4* out) {
     if (!c->sum_done) RZ_HIP(c, hipEventCreateWithFlags(&c->sum_done, hipEventDisableTiming));
     for (uint32_t r = 0; r < n_staged; ++r) {
         hiprz_ctx* p = c->peers[r];
-        if (p->n_local_tiles != c->n_local_tiles || !p->accum.ptr) return fail(c, HIPRZ_ERR_STATE, "sample sharding: a part's share differs from the head's");
+        if (p->n_local_tiles != c->n_local_tiles || !buffer_of(p)) return fail(c, HIPRZ_ERR_STATE, "sample sharding: a part's share differs from the head's");
         (void)hipSetDevice(p->device);
         if (c->sum_recorded) RZ_HIP(c, hipStreamWaitEvent(p->stream, c->sum_done, 0));
-        RZ_HIP(c, hipMemcpyPeerAsync(staged + n * r, c->device, p->accum.ptr, p->device, n * sizeof(float4), p->stream));
+        RZ_HIP(c, hipMemcpyPeerAsync(staged + n * r, c->device, buffer_of(p), p->device, n * sizeof(float4), p->stream));
         RZ_HIP(c, hipEventRecord(p->peer_done, p->stream));
         (void)hipSetDevice(c->device);
         RZ_HIP(c, hipStreamWaitEvent(c->stream, p->peer_done, 0));
     }
-    RZ_LAUNCH(rz_sum_parts_kernel, dim3(c->n_local_tiles), dim3(256), 0, c->stream, c->accum.ptr, staged, n, n_staged, out, uint32_t(n));
+    RZ_LAUNCH(rz_sum_parts_kernel, dim3(c->n_local_tiles), dim3(256), 0, c->stream, buffer_of(c), staged, n, n_staged, out, uint32_t(n));
     RZ_HIP(c, hipGetLastError());
     RZ_HIP(c, hipEventRecord(c->sum_done, c->stream));
     c->sum_recorded = true;
     return HIPRZ_OK;
+}
+int sum_parts(hiprz_ctx* c, float4* out) {
+    return sum_parts_of(c, out, [](hiprz_ctx* p) { return (const float4*)p->accum.ptr; });
 }
 template <typename T, typename Tiles>
 int export_tiles(hiprz_ctx* c, void* dst_device, size_t bytes, const char* what, Tiles tiles_of) {
@@ -1272,6 +1345,43 @@ int assemble_accum_image(hiprz_ctx* c) {
         tiles = c->sum_accum.ptr;
     }
     return assemble_untiled<float4>(c, tiles, [](hiprz_ctx* p) { return (const float4*)p->accum.ptr; });
+}
+// Tile mode: every part turns its own pixels' moments into the estimate on its stream and the tiles are assembled as the accumulator's
+// are.  Sample mode: the parts' batches are just more batches — accumulator and moments are summed in part order (K included) and the
+// formula runs on the sums.  Before the first render call after a restart there is no estimate: zeros.
+int assemble_variance_image(hiprz_ctx* c) {
+    (void)hipSetDevice(c->device);
+    const size_t pixels = size_t(c->camera.width) * c->camera.height, n = size_t(c->n_local_tiles) * 256u;
+    RZ_HIP(c, c->var_image.resize(pixels));
+    if (c->reset_pending || !c->var_m0.ptr || c->var_m0.count < n || !n) {
+        RZ_HIP(c, hipMemsetAsync(c->var_image.ptr, 0, pixels * sizeof(float4), c->stream));
+        return HIPRZ_OK;
+    }
+    const auto var_tiles_of = [](hiprz_ctx* p) { return (const float4*)p->var_tiles.ptr; };
+    RZ_HIP(c, c->var_tiles.resize(n));
+    if (samples_head(c)) {
+        RZ_HIP(c, c->sum_accum.resize(n));
+        RZ_HIP(c, c->sum_m0.resize(n));
+        RZ_HIP(c, c->sum_m1.resize(n));
+        if (const int rc = sum_parts(c, c->sum_accum.ptr); rc != HIPRZ_OK) return rc;
+        if (const int rc = sum_parts_of(c, c->sum_m0.ptr, [](hiprz_ctx* p) { return (const float4*)p->var_m0.ptr; }); rc != HIPRZ_OK) return rc;
+        if (const int rc = sum_parts_of(c, c->sum_m1.ptr, [](hiprz_ctx* p) { return (const float4*)p->var_m1.ptr; }); rc != HIPRZ_OK) return rc;
+        RZ_LAUNCH(rz_variance_kernel, dim3(c->n_local_tiles), dim3(256), 0, c->stream, c->sum_accum.ptr, c->sum_m0.ptr, c->sum_m1.ptr, c->var_tiles.ptr, uint32_t(n));
+        RZ_HIP(c, hipGetLastError());
+        return assemble_untiled<float4>(c, c->var_tiles.ptr, var_tiles_of, c->var_image.ptr);
+    }
+    RZ_LAUNCH(rz_variance_kernel, dim3(c->n_local_tiles), dim3(256), 0, c->stream, c->accum.ptr, c->var_m0.ptr, c->var_m1.ptr, c->var_tiles.ptr, uint32_t(n));
+    for (hiprz_ctx* p : c->peers) {
+        const size_t local = size_t(p->n_local_tiles) * 256u;
+        if (!local) continue;
+        if (!p->var_m0.ptr || p->var_m0.count < local) return fail(c, HIPRZ_ERR_STATE, "variance: a part holds no moments");
+        (void)hipSetDevice(p->device);
+        RZ_HIP(c, p->var_tiles.resize(local));
+        RZ_LAUNCH(rz_variance_kernel, dim3(p->n_local_tiles), dim3(256), 0, p->stream, p->accum.ptr, p->var_m0.ptr, p->var_m1.ptr, p->var_tiles.ptr, uint32_t(local));
+    }
+    (void)hipSetDevice(c->device);
+    RZ_HIP(c, hipGetLastError());
+    return assemble_untiled<float4>(c, c->var_tiles.ptr, var_tiles_of, c->var_image.ptr);
 }
 }  // namespace hiprz
 
@@ -2310,6 +2420,52 @@ int hiprz_reset(hiprz_ctx* c) {
     return HIPRZ_OK;
 }
 
+int hiprz_set_variance(hiprz_ctx* c, int enabled) {
+    if (!c) return HIPRZ_ERR_INVALID;
+    RZ_FANOUT(c, hiprz_set_variance(p, enabled));
+    const bool on = enabled != 0;
+    if (on == c->variance_on) return HIPRZ_OK;
+    c->variance_on = on;
+    stale_guides(c);
+    c->reset_pending = true;  // the moments belong to one accumulation, from its first batch on
+    for (auto& f : c->parked) f.reset_pending = true;
+    if (!on) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);  // an enqueued batch may still write them
+        release_variance(c);
+        for (auto& f : c->parked) release_variance(&f);
+    }
+    return HIPRZ_OK;
+}
+
+namespace {
+int check_variance(hiprz_ctx* c, const char* what) {
+    if (c->is_peer) return fail(c, HIPRZ_ERR_STATE, std::string(what) + " on a part of a multi-device context");
+    if (!c->variance_on) return fail(c, HIPRZ_ERR_STATE, std::string(what) + ": hiprz_set_variance is off");
+    if (!c->have_scene || !c->have_camera) return fail(c, HIPRZ_ERR_STATE, std::string(what) + " before scene and camera upload");
+    return HIPRZ_OK;
+}
+}  // namespace
+
+int hiprz_read_variance(hiprz_ctx* c, float* dst, size_t bytes) {
+    if (!c) return HIPRZ_ERR_INVALID;
+    if (const int rc = check_variance(c, "read_variance"); rc != HIPRZ_OK) return rc;
+    if (!dst || bytes != size_t(c->camera.width) * c->camera.height * sizeof(float4)) return fail(c, HIPRZ_ERR_INVALID, "read_variance: destination size mismatch");
+    if (const int rc = assemble_variance_image(c); rc != HIPRZ_OK) return rc;
+    RZ_HIP(c, hipMemcpyAsync(dst, c->var_image.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    return HIPRZ_OK;
+}
+
+int hiprz_variance_device(hiprz_ctx* c, const void** out) {
+    if (!c) return HIPRZ_ERR_INVALID;
+    if (!out) return fail(c, HIPRZ_ERR_INVALID, "variance_device: null output");
+    if (const int rc = check_variance(c, "variance_device"); rc != HIPRZ_OK) return rc;
+    if (const int rc = assemble_variance_image(c); rc != HIPRZ_OK) return rc;
+    *out = c->var_image.ptr;
+    return HIPRZ_OK;
+}
+
 int hiprz_render(hiprz_ctx* c, uint32_t n_passes) {
     if (!c) return HIPRZ_ERR_INVALID;
     if (!c->peers.empty() && n_passes) {
@@ -2590,6 +2746,8 @@ int hiprz_present(hiprz_ctx* c, uint32_t x, uint32_t y) {
     if (c->denoise_on && c->user_world > 1u)  // refused before anything is enqueued: the slots and the sequence stay as they are
         return fail(c, HIPRZ_ERR_STATE, "present: hiprz_set_denoise is set, but this context renders shard " + std::to_string(c->user_rank) + " of " +
                                             std::to_string(c->user_world) + " and does not hold the frame (clear it, or gather and hiprz_denoise_image)");
+    if (c->denoise_on && (c->denoise_params.flags & HIPRZ_DENOISE_VARIANCE) && !c->variance_on)  // likewise
+        return fail(c, HIPRZ_ERR_STATE, "present: hiprz_set_denoise asks for HIPRZ_DENOISE_VARIANCE, but hiprz_set_variance is off");
     (void)hipSetDevice(c->device);
     for (const auto& s : c->frame_slot)  // a copy of an earlier present that failed on the device
         if (s.copy_enqueued) {

@@ -177,6 +177,11 @@ struct hiprz_frame_state {
     hiprz::DeviceArray<float4> dn_out;
     hiprz::DeviceArray<uint32_t> dn_rgba8;
     bool dn_valid = false;  // dn_out / dn_rgba8 hold a denoised frame of this camera at its current size
+    // hiprz_set_variance: batch moments of the accumulator, tile-major beside `accum` (include/hiprz.h "VARIANCE"), allocated by the first
+    // render call while it is on — snap: the accumulator when the pixel's last batch closed; m0 = (S2_r, S2_g, S2_b, SA); m1 = (S1_r, S1_g,
+    // S1_b, K) — the estimate of this part's pixels (tile-major), and on the head its row-major image and, under HIPRZ_SHARD_SAMPLES,
+    // the parts' moments summed
+    hiprz::DeviceArray<float4> var_snap, var_m0, var_m1, var_tiles, var_image, sum_m0, sum_m1;
 };
 
 struct hiprz_ctx : hiprz_frame_state {
@@ -213,6 +218,7 @@ struct hiprz_ctx : hiprz_frame_state {
     hiprz::DeviceArray<float4> dn_tmp[2];
     bool denoise_on = false;
     hiprz_denoise_params denoise_params{};
+    bool variance_on = false;  // hiprz_set_variance
 
     // cameras (hiprz_set_camera_count / hiprz_select_camera)
     std::vector<hiprz_frame_state> parked;  // slot [active_camera] is empty while that camera's state lives in the context itself
@@ -395,6 +401,8 @@ int assemble_accum_image(hiprz_ctx* c);
 // denoising: rz_guide_kernel into c->guides when they are stale (hiprz_launch_guide.hip); the filter on `stream` (hiprz_denoise.hip)
 int ensure_guides(hiprz_ctx* c);
 int denoise_frame(hiprz_ctx* c, const hiprz_denoise_params* params, uint32_t* rgba8_out);
+// the selected camera's variance estimate as hiprz_read_variance defines it, row-major in c->var_image on the context's stream (hiprz_api.hip)
+int assemble_variance_image(hiprz_ctx* c);
 int sort_workspace(hiprz_ctx* c, size_t n);  // (re)allocates the sort's buffers for n keys
 int sort_temp_resize(hiprz_ctx* c, hiprz_frame_state::SortTemp& t, size_t n);
 void sort_u32(hipStream_t stream, uint32_t* keys, uint32_t n, int key_bits, uint32_t* perm, uint32_t* sorted_keys, hiprz_frame_state::SortTemp& t);  // keys destroyed

@@ -20,21 +20,33 @@ int check_params(hiprz_ctx* c, const hiprz_denoise_params& p) {
     if (!(p.sigma_normal >= 0.0f) || !(p.sigma_depth >= 0.0f) || !(p.sigma_color >= 0.0f) || std::isinf(p.sigma_normal) || std::isinf(p.sigma_depth) ||
         std::isinf(p.sigma_color))
         return fail(c, HIPRZ_ERR_INVALID, "denoise: the sigmas must be finite and not negative");
-    if (p.flags & ~HIPRZ_DENOISE_DEMODULATE) return fail(c, HIPRZ_ERR_INVALID, "denoise: unknown flag");
+    if (p.flags & ~(HIPRZ_DENOISE_DEMODULATE | HIPRZ_DENOISE_VARIANCE)) return fail(c, HIPRZ_ERR_INVALID, "denoise: unknown flag");
     return HIPRZ_OK;
 }
 
-template <bool FIRST, bool LAST>
+template <bool FIRST, bool LAST, bool VARIANCE>
 void launch_iteration(const DenoiseArgs& a, hipStream_t stream) {
     const uint32_t s = 1u << a.shift;
     const uint32_t sub_w = (a.width + s - 1u) / s, sub_h = (a.height + s - 1u) / s;
     const dim3 grid(((sub_w + kDenoiseTileW - 1u) / kDenoiseTileW) << a.shift, ((sub_h + kDenoiseTileH - 1u) / kDenoiseTileH) << a.shift);
-    RZ_LAUNCH((rz_atrous_kernel<FIRST, LAST>), grid, dim3(256), 0, stream, a);
+    RZ_LAUNCH((rz_atrous_kernel<FIRST, LAST, VARIANCE>), grid, dim3(256), 0, stream, a);
 }
 
-// the filter: src (accumulator image) -> dst (+ its tone map into rgba8 when given), guides as given, on `stream`
-int run_filter(hiprz_ctx* c, const float4* src, const float4* guides, const hiprz_denoise_params& p, float4* dst, uint32_t* rgba8, hipStream_t stream) {
+template <bool VARIANCE>
+void launch_iteration(const DenoiseArgs& a, bool first, bool last, hipStream_t stream) {
+    if (first && last) launch_iteration<true, true, VARIANCE>(a, stream);
+    else if (first) launch_iteration<true, false, VARIANCE>(a, stream);
+    else if (last) launch_iteration<false, true, VARIANCE>(a, stream);
+    else launch_iteration<false, false, VARIANCE>(a, stream);
+}
+
+// the filter: src (accumulator image) -> dst (+ its tone map into rgba8 when given), guides as given, on `stream`; `variance`: the
+// estimate's image under HIPRZ_DENOISE_VARIANCE
+int run_filter(hiprz_ctx* c, const float4* src, const float4* guides, const float4* variance, const hiprz_denoise_params& p, float4* dst, uint32_t* rgba8,
+               hipStream_t stream) {
     if (const int rc = check_params(c, p); rc != HIPRZ_OK) return rc;
+    const bool guided = (p.flags & HIPRZ_DENOISE_VARIANCE) != 0u;
+    if (guided != (variance != nullptr)) return fail(c, HIPRZ_ERR_INVALID, "denoise: HIPRZ_DENOISE_VARIANCE and the variance image go together");
     const uint32_t W = c->camera.width, H = c->camera.height;
     const size_t n = size_t(W) * H;
     for (uint32_t k = 0; k + 1u < p.iterations && k < 2u; ++k) RZ_HIP(c, c->dn_tmp[k].resize(n));
@@ -44,6 +56,7 @@ int run_filter(hiprz_ctx* c, const float4* src, const float4* guides, const hipr
     a.tone_k = ((c->camera.aperture * c->camera.aperture * RZ_PI_F) * c->camera.exposure_time) * 1.0e5f;
     a.demodulate = (p.flags & HIPRZ_DENOISE_DEMODULATE) ? 1u : 0u;
     a.aperture = c->camera.aperture, a.exposure_time = c->camera.exposure_time;
+    a.variance = variance, a.sigma_lum = p.sigma_color;
     for (uint32_t i = 0; i < p.iterations; ++i) {
         const bool first = i == 0u, last = i + 1u == p.iterations;
         a.src = first ? src : c->dn_tmp[(i - 1u) & 1u].ptr;
@@ -52,10 +65,8 @@ int run_filter(hiprz_ctx* c, const float4* src, const float4* guides, const hipr
         a.shift = i;
         const float scale = p.sigma_color / float(1u << i);
         a.color_scale2 = scale * scale;
-        if (first && last) launch_iteration<true, true>(a, stream);
-        else if (first) launch_iteration<true, false>(a, stream);
-        else if (last) launch_iteration<false, true>(a, stream);
-        else launch_iteration<false, false>(a, stream);
+        if (guided) launch_iteration<true>(a, first, last, stream);
+        else launch_iteration<false>(a, first, last, stream);
     }
     RZ_HIP(c, hipGetLastError());
     return HIPRZ_OK;
@@ -78,13 +89,17 @@ int denoise_frame(hiprz_ctx* c, const hiprz_denoise_params* params, uint32_t* rg
                                             " and does not hold the frame (gather it, then hiprz_denoise_image)");
     const hiprz_denoise_params p = params ? *params : kDefaultParams;
     if (const int rc = check_params(c, p); rc != HIPRZ_OK) return rc;
+    const bool guided = (p.flags & HIPRZ_DENOISE_VARIANCE) != 0u;
+    if (guided && !c->variance_on) return fail(c, HIPRZ_ERR_STATE, "denoise: HIPRZ_DENOISE_VARIANCE needs the estimate of hiprz_set_variance, which is off");
     if (const int rc = ensure_guides(c); rc != HIPRZ_OK) return rc;
+    if (guided)
+        if (const int rc = assemble_variance_image(c); rc != HIPRZ_OK) return rc;
     if (const int rc = assemble_accum_image(c); rc != HIPRZ_OK) return rc;
     (void)hipSetDevice(c->device);
     const size_t n = size_t(c->camera.width) * c->camera.height;
     RZ_HIP(c, c->dn_out.resize(n));
     RZ_HIP(c, c->dn_rgba8.resize(n));
-    if (const int rc = run_filter(c, c->image_f4.ptr, c->guides.ptr, p, c->dn_out.ptr, c->dn_rgba8.ptr, c->stream); rc != HIPRZ_OK) return rc;
+    if (const int rc = run_filter(c, c->image_f4.ptr, c->guides.ptr, guided ? c->var_image.ptr : nullptr, p, c->dn_out.ptr, c->dn_rgba8.ptr, c->stream); rc != HIPRZ_OK) return rc;
     if (rgba8_out) RZ_HIP(c, hipMemcpyAsync(rgba8_out, c->dn_rgba8.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     c->dn_valid = true;
     return HIPRZ_OK;
@@ -103,17 +118,25 @@ int hiprz_denoise(hiprz_ctx* c, const hiprz_denoise_params* params) {
     return denoise_frame(c, params, nullptr);
 }
 
-int hiprz_denoise_image(hiprz_ctx* c, const void* accum_image, const void* guides, const hiprz_denoise_params* params, void* dst, void* stream) {
-    if (!c) return HIPRZ_ERR_INVALID;
+namespace {
+int denoise_image(hiprz_ctx* c, const void* accum_image, const void* guides, const void* variance, bool guided, const hiprz_denoise_params* params, void* dst,
+                  void* stream) {
     if (const int rc = check_frame_holder(c, "denoise_image"); rc != HIPRZ_OK) return rc;
     if (!accum_image || !dst || accum_image == dst) return fail(c, HIPRZ_ERR_INVALID, "denoise_image: null or aliased image");
+    if (guided && (!variance || variance == dst)) return fail(c, HIPRZ_ERR_INVALID, "denoise_image_variance: null or aliased variance image");
+    {
+        const hiprz_denoise_params q = params ? *params : kDefaultParams;
+        if (const int rc = check_params(c, q); rc != HIPRZ_OK) return rc;
+        if (guided && !(q.flags & HIPRZ_DENOISE_VARIANCE)) return fail(c, HIPRZ_ERR_INVALID, "denoise_image_variance: HIPRZ_DENOISE_VARIANCE is not set");
+        if (!guided && (q.flags & HIPRZ_DENOISE_VARIANCE)) return fail(c, HIPRZ_ERR_INVALID, "denoise_image: HIPRZ_DENOISE_VARIANCE takes hiprz_denoise_image_variance");
+    }
     if (!guides) {
         if (const int rc = ensure_guides(c); rc != HIPRZ_OK) return rc;
         guides = c->guides.ptr;
     }
     (void)hipSetDevice(c->device);
     hipStream_t on = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    if (on != c->stream && guides == c->guides.ptr) {  // the context's guides were enqueued on its own stream
+    if (on != c->stream && (guides == c->guides.ptr || (variance && variance == c->var_image.ptr))) {  // the context's guides (its estimate) were enqueued on its own stream
         hipEvent_t e = nullptr;
         RZ_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         RZ_HIP(c, hipEventRecord(e, c->stream));
@@ -121,7 +144,20 @@ int hiprz_denoise_image(hiprz_ctx* c, const void* accum_image, const void* guide
         RZ_HIP(c, hipEventDestroy(e));
     }
     const hiprz_denoise_params p = params ? *params : kDefaultParams;
-    return run_filter(c, static_cast<const float4*>(accum_image), static_cast<const float4*>(guides), p, static_cast<float4*>(dst), nullptr, on);
+    return run_filter(c, static_cast<const float4*>(accum_image), static_cast<const float4*>(guides), static_cast<const float4*>(variance), p,
+                      static_cast<float4*>(dst), nullptr, on);
+}
+}  // namespace
+
+int hiprz_denoise_image(hiprz_ctx* c, const void* accum_image, const void* guides, const hiprz_denoise_params* params, void* dst, void* stream) {
+    if (!c) return HIPRZ_ERR_INVALID;
+    return denoise_image(c, accum_image, guides, nullptr, false, params, dst, stream);
+}
+
+int hiprz_denoise_image_variance(hiprz_ctx* c, const void* accum_image, const void* guides, const void* variance_image, const hiprz_denoise_params* params,
+                                 void* dst, void* stream) {
+    if (!c) return HIPRZ_ERR_INVALID;
+    return denoise_image(c, accum_image, guides, variance_image, true, params, dst, stream);
 }
 
 int hiprz_read_denoised(hiprz_ctx* c, float* dst, size_t bytes) {

@@ -10,6 +10,11 @@
 // neighbours in the grid (blockIdx = tile * s + class), so the cache lines they share — a class uses every s-th record of a line — are
 // fetched while hot.  The first iteration divides by the sample count and the albedo on the way in, the last multiplies the albedo back
 // and tone-maps on the way out: neither costs a pass over the image.
+//
+// HIPRZ_DENOISE_VARIANCE (include/hiprz.h "THE VARIANCE-GUIDED FILTER") is a third instantiation axis on the same scheme and the same
+// record: the tone-curved colour is unused there, so its slot carries lum(c_i) and v_i; the intermediate iterates' alpha, constant 1 and
+// never read otherwise, carries v_i from one iteration to the next.  g_i, the weights and both sums come from the taps already staged —
+// a first sweep over the 25 records' third quarter for g_i, then the sweep of the plain filter.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,12 +35,14 @@ struct DenoiseArgs {
     float tone_k;          // pi * aperture^2 * exposure_time * 1e5
     uint32_t demodulate;
     float aperture, exposure_time;
+    const float4* variance;  // VARIANCE, iteration 0: (V_r, V_g, V_b, K) per pixel (hiprz_read_variance)
+    float sigma_lum;         // VARIANCE: sigma_color, in standard deviations
 };
 
 struct DenoiseTap {
     float4 c;  // current iterate rgb, bits(instance)
     float4 n;  // normal, depth
-    float4 t;  // tone curve of c per channel, 1 = the tap lies in the frame
+    float4 t;  // tone curve of c per channel, 1 = the tap lies in the frame; VARIANCE: (lum(c), v, 0, 1)
 };
 
 RZ_DEV float denoise_tone(float k, float c) {
@@ -43,9 +50,10 @@ RZ_DEV float denoise_tone(float k, float c) {
     return kc / (kc + 1.0f);
 }
 RZ_DEV float denoise_albedo(float a) { return fmaxf(a, 0.01f); }
+RZ_DEV float denoise_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
 // the record of pixel (x, y), which lies in the frame
-template <bool FIRST>
+template <bool FIRST, bool VARIANCE>
 RZ_DEV DenoiseTap denoise_load(const DenoiseArgs& a, uint32_t x, uint32_t y) {
     const size_t i = size_t(y) * a.width + x;
     const float4 v = a.src[i], g0 = a.guides[2u * i], g1 = a.guides[2u * i + 1u];
@@ -58,7 +66,22 @@ RZ_DEV DenoiseTap denoise_load(const DenoiseArgs& a, uint32_t x, uint32_t y) {
     DenoiseTap tap;
     tap.c = make_float4(r, g, b, g1.w);
     tap.n = g0;
-    tap.t = make_float4(denoise_tone(a.tone_k, r), denoise_tone(a.tone_k, g), denoise_tone(a.tone_k, b), 1.0f);
+    if constexpr (VARIANCE) {
+        float var = v.w;  // the previous iteration left v_i in the alpha channel
+        if constexpr (FIRST) {
+            const float4 V = a.variance[i];
+            var = -1.0f;
+            if (V.w >= 2.0f) {
+                float sr = sqrtf(V.x), sg = sqrtf(V.y), sb = sqrtf(V.z);
+                if (a.demodulate) sr = sr / denoise_albedo(g1.x), sg = sg / denoise_albedo(g1.y), sb = sb / denoise_albedo(g1.z);
+                const float sd = denoise_lum(sr, sg, sb);
+                var = sd * sd;
+            }
+        }
+        tap.t = make_float4(denoise_lum(r, g, b), var, 0.0f, 1.0f);
+    } else {
+        tap.t = make_float4(denoise_tone(a.tone_k, r), denoise_tone(a.tone_k, g), denoise_tone(a.tone_k, b), 1.0f);
+    }
     return tap;
 }
 
@@ -80,10 +103,25 @@ RZ_DEV void denoise_accumulate(const DenoiseArgs& a, const DenoiseTap& p, float 
     }
     sum.r = sum.r + w * q.c.x, sum.g = sum.g + w * q.c.y, sum.b = sum.b + w * q.c.z, sum.w = sum.w + w;
 }
+// the same under HIPRZ_DENOISE_VARIANCE: w_l in the place of w_c, and sum w^2 v beside the sums
+RZ_DEV void denoise_accumulate_variance(const DenoiseArgs& a, const DenoiseTap& p, float depth_scale, float lum_scale, const DenoiseTap& q, float spline, DenoiseSum& sum,
+                                        float& sum_v) {
+    const uint32_t instance = __float_as_uint(p.c.w);
+    if (q.t.w == 0.0f || __float_as_uint(q.c.w) != instance) return;
+    float w = spline;
+    if (instance != HIPRZ_GUIDE_MISS) {
+        w = w * RZ_POWF(fmaxf(0.0f, p.n.x * q.n.x + p.n.y * q.n.y + p.n.z * q.n.z), a.sigma_normal);
+        w = w * RZ_EXPF(-(fabsf(p.n.w - q.n.w) / depth_scale));
+    }
+    if (p.t.y >= 0.0f) w = w * RZ_EXPF(-(fabsf(p.t.x - q.t.x) / lum_scale));
+    sum.r = sum.r + w * q.c.x, sum.g = sum.g + w * q.c.y, sum.b = sum.b + w * q.c.z, sum.w = sum.w + w;
+    sum_v = sum_v + (w * w) * fmaxf(q.t.y, 0.0f);
+}
 RZ_DEV float denoise_spline(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
 
+// alpha: 1, or under HIPRZ_DENOISE_VARIANCE the next iteration's v
 template <bool LAST>
-RZ_DEV void denoise_store(const DenoiseArgs& a, uint32_t x, uint32_t y, const DenoiseSum& sum) {
+RZ_DEV void denoise_store(const DenoiseArgs& a, uint32_t x, uint32_t y, const DenoiseSum& sum, float alpha = 1.0f) {
     const size_t i = size_t(y) * a.width + x;
     float r = sum.r / sum.w, g = sum.g / sum.w, b = sum.b / sum.w;
     if constexpr (LAST) {
@@ -93,7 +131,7 @@ RZ_DEV void denoise_store(const DenoiseArgs& a, uint32_t x, uint32_t y, const De
         }
         if (a.rgba8) a.rgba8[i] = tonemap(col4{r, g, b, 1.0f}, a.aperture, a.exposure_time);
     }
-    a.dst[i] = make_float4(r, g, b, 1.0f);
+    a.dst[i] = make_float4(r, g, b, LAST ? 1.0f : alpha);
 }
 
 constexpr uint32_t kDenoiseTileW = 32u, kDenoiseTileH = 8u, kDenoiseHalo = 2u;
@@ -101,7 +139,7 @@ constexpr uint32_t kDenoiseLdsW = kDenoiseTileW + 2u * kDenoiseHalo, kDenoiseLds
 constexpr uint32_t kDenoiseLdsRecords = kDenoiseLdsW * kDenoiseLdsH;
 
 // grid: (tiles_x << shift, tiles_y << shift) with tiles over the sub-lattice of ceil(W / s) x ceil(H / s) pixels
-template <bool FIRST, bool LAST>
+template <bool FIRST, bool LAST, bool VARIANCE>
 __global__ void __launch_bounds__(256) rz_atrous_kernel(const DenoiseArgs a) {
     __shared__ float4 lds_c[kDenoiseLdsRecords], lds_n[kDenoiseLdsRecords], lds_t[kDenoiseLdsRecords];
     const uint32_t s_mask = (1u << a.shift) - 1u;
@@ -113,7 +151,7 @@ __global__ void __launch_bounds__(256) rz_atrous_kernel(const DenoiseArgs a) {
         tap.c = tap.n = tap.t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (sx >= 0 && sy >= 0) {
             const uint32_t x = ox + (uint32_t(sx) << a.shift), y = oy + (uint32_t(sy) << a.shift);
-            if (x < a.width && y < a.height) tap = denoise_load<FIRST>(a, x, y);
+            if (x < a.width && y < a.height) tap = denoise_load<FIRST, VARIANCE>(a, x, y);
         }
         lds_c[i] = tap.c, lds_n[i] = tap.n, lds_t[i] = tap.t;
     }
@@ -125,6 +163,42 @@ __global__ void __launch_bounds__(256) rz_atrous_kernel(const DenoiseArgs a) {
     const DenoiseTap p{lds_c[centre], lds_n[centre], lds_t[centre]};
     const float depth_scale = a.sigma_depth * p.n.w + 1.0e-6f;
     DenoiseSum sum{0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (VARIANCE) {
+        float lum_scale = 1.0f, sum_v = 0.0f;
+        if (p.t.y >= 0.0f) {  // g_i(p): the spline average of v_i over the taps that have an estimate (the centre is one of them)
+            const uint32_t instance = __float_as_uint(p.c.w);
+            float gv = 0.0f, gk = 0.0f;
+#pragma unroll
+            for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+                for (int dx = -2; dx <= 2; ++dx) {
+                    const uint32_t j = uint32_t(int(centre) + dy * int(kDenoiseLdsW) + dx);
+                    const float4 t = lds_t[j];
+                    if (t.w == 0.0f || !(t.y >= 0.0f) || __float_as_uint(lds_c[j].w) != instance) continue;
+                    const float spline = denoise_spline(dx) * denoise_spline(dy);
+                    gv = gv + spline * t.y, gk = gk + spline;
+                }
+            }
+            lum_scale = a.sigma_lum * sqrtf(gv / gk) + 1.0e-10f;
+        }
+#pragma unroll
+        for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; ++dx) {
+                const float spline = denoise_spline(dx) * denoise_spline(dy);
+                if (dx == 0 && dy == 0) {
+                    sum.r = sum.r + spline * p.c.x, sum.g = sum.g + spline * p.c.y, sum.b = sum.b + spline * p.c.z, sum.w = sum.w + spline;
+                    sum_v = sum_v + (spline * spline) * fmaxf(p.t.y, 0.0f);
+                    continue;
+                }
+                const uint32_t j = uint32_t(int(centre) + dy * int(kDenoiseLdsW) + dx);
+                const DenoiseTap q{lds_c[j], lds_n[j], lds_t[j]};
+                denoise_accumulate_variance(a, p, depth_scale, lum_scale, q, spline, sum, sum_v);
+            }
+        }
+        denoise_store<LAST>(a, x, y, sum, p.t.y >= 0.0f ? sum_v / (sum.w * sum.w) : -1.0f);
+        return;
+    }
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll

@@ -43,8 +43,9 @@ TREE_REFERENCE, TREE_SAH, TREE_DEVICE, TREE_DEVICE_SAH, TREE_AUTO = range(5)   #
 SHARD_TILES, SHARD_SAMPLES = 0, 1   # hiprz_set_shard_mode
 
 
-def denoise_params(iterations=None, sigma_normal=None, sigma_depth=None, sigma_color=None, demodulate=None):
-    """hiprz_denoise_params: the library's defaults (hiprz_denoise_default_params) with the given fields replaced."""
+def denoise_params(iterations=None, sigma_normal=None, sigma_depth=None, sigma_color=None, demodulate=None, variance=None):
+    """hiprz_denoise_params: the library's defaults (hiprz_denoise_default_params) with the given fields replaced.  `variance`: the
+    variance-guided filter (DENOISE_VARIANCE), whose sigma_color is a luminance tolerance in standard deviations."""
     p = _abi.DenoiseParams()
     _lib.load().hiprz_denoise_default_params(C.byref(p))
     if iterations is not None:
@@ -54,7 +55,13 @@ def denoise_params(iterations=None, sigma_normal=None, sigma_depth=None, sigma_c
             setattr(p, name, float(value))
     if demodulate is not None:
         p.flags = (p.flags & ~_abi.DENOISE_DEMODULATE) | (_abi.DENOISE_DEMODULATE if demodulate else 0)
+    if variance is not None:
+        p.flags = (p.flags & ~_abi.DENOISE_VARIANCE) | (_abi.DENOISE_VARIANCE if variance else 0)
     return p
+
+
+def _wants_variance(params):
+    return params is not None and bool(params.flags & _abi.DENOISE_VARIANCE)
 
 
 def default_streams(n_lights):
@@ -359,6 +366,26 @@ class Context:
         """While set (params not None), present() delivers the denoised image in the frame's rgba8; None clears it."""
         self._check(self.lib.hiprz_set_denoise(self._ctx, self._params(params)))
 
+    def denoise_image_variance(self, accum_ptr, guides_ptr, variance_ptr, params, dst_ptr, stream=None):
+        """The variance-guided filter on device images: as denoise_image, plus a W*H float4 variance image (read_variance's layout)."""
+        self._check(self.lib.hiprz_denoise_image_variance(self._ctx, accum_ptr, guides_ptr, variance_ptr, self._params(params), dst_ptr, stream))
+
+    # --- variance: batch moments of the accumulator, one batch per render call (include/hiprz.h "VARIANCE") ---
+    def set_variance(self, enabled):
+        """hiprz_set_variance: a real change restarts accumulation."""
+        self._check(self.lib.hiprz_set_variance(self._ctx, int(bool(enabled))))
+
+    def read_variance(self):
+        """(H, W, 4) float32: the variance of the mean radiance per channel and the number of closed batches K (0 variance where K < 2)."""
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        self._check(self.lib.hiprz_read_variance(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def variance_device(self):
+        v = C.c_void_p()
+        self._check(self.lib.hiprz_variance_device(self._ctx, C.byref(v)))
+        return v.value
+
     def selftest(self, cases_per_thread=64, seed=1):
         bad, n = C.c_uint64(), C.c_uint64()
         self._check(self.lib.hiprz_selftest(self._ctx, cases_per_thread, seed, C.byref(bad), C.byref(n)))
@@ -440,7 +467,8 @@ class Engine:
         the GPU, None = default_streams() of the first world rendered; asking for `engine.context` before that settles for one.
         `pipelined`: frames leave through Context.present / read_frame, and renderWorld(sync=False) hands out the PREVIOUS call's frame
         while this call's renders (the C++ engine's sync=false); the default reads every frame synchronously and ignores `sync`.
-        `denoise`: None, or _abi.DenoiseParams (denoise_params()): the cameras' image buffers receive the denoised frame, on both paths."""
+        `denoise`: None, or _abi.DenoiseParams (denoise_params()): the cameras' image buffers receive the denoised frame, on both paths
+        (with variance=True the context's variance estimate is switched on: every renderWorld call is one batch)."""
         self._device, self._streams, self._context = device, streams, None
         self._denoise = denoise
         self._pipelined = pipelined
@@ -455,14 +483,19 @@ class Engine:
         if self._context is None:
             self._context = Context(self._device)
             self._context.set_tree(self._tree)
-            self._context.set_denoise(self._denoise)
+            self._apply_denoise()
         return self._context
 
     def set_denoise(self, params):
         """None, or the parameters of the filter whose output the cameras' image buffers receive from the next frame on."""
         self._denoise = params
         if self._context is not None:
-            self._context.set_denoise(params)
+            self._apply_denoise()
+
+    def _apply_denoise(self):
+        """the context's filter parameters, and its variance estimate on exactly while they ask for the variance-guided filter"""
+        self._context.set_variance(_wants_variance(self._denoise))
+        self._context.set_denoise(self._denoise)
 
     def set_tree(self, tree):
         """Context.set_tree for the engine's context (default TREE_AUTO); takes effect at the next scene upload, which this forces."""
@@ -482,7 +515,7 @@ class Engine:
             k = self._streams or default_streams(len(world.spot_lights) + len(world.direct_lights))
             self._context = Context([self._device] * k) if k > 1 else Context(self._device)
             self._context.set_tree(self._tree)
-            self._context.set_denoise(self._denoise)
+            self._apply_denoise()
             if getattr(self, "_mode", 0):
                 self._context.set_mode(self._mode)
         ctx = self.context
