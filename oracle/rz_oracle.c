@@ -21,6 +21,73 @@
 #endif
 
 /* All transcendental calls go through these (glibc's libm on the CPU side; the device build uses ocml). */
+#ifdef RZ_NUDGE_ULPS
+/* Stand-ins for another libm (tests/lockstep.py: the caps of the lockstep comparison).  Every call is evaluated in double and rounded to
+ * float; a result that IS a float (powf(x, 0), cosf(0), acosf(1): exact in every libm, and a roughness-0 mirror depends on it) stays, every
+ * other one moves n ulps: down (RZ_NUDGE_DIR < 0), up (> 0), or one of the two chosen by a hash of the argument's bits (0).  n is
+ * RZ_NUDGE_ULPS, or RZ_NUDGE_<FUNCTION> where a function of the device's library lies further from glibc's (Oracle). */
+#ifndef RZ_NUDGE_DIR
+#define RZ_NUDGE_DIR 0
+#endif
+static inline float rz_nudge(double exact, float arg, float arg2, int n) {
+    float f = (float)exact;
+    if ((double)f == exact || f != f) return f;
+    int up = RZ_NUDGE_DIR > 0;
+    if (RZ_NUDGE_DIR == 0) {
+        uint32_t a, b;
+        memcpy(&a, &arg, 4);
+        memcpy(&b, &arg2, 4);
+        uint32_t h = (a ^ (b * 0x9E3779B9u)) * 0x7feb352dU;
+        h ^= h >> 15;
+        h *= 0x846ca68bU;
+        up = (int)((h >> 16) & 1u);
+    }
+    for (int i = 0; i < n; ++i) f = nextafterf(f, up ? INFINITY : -INFINITY);
+    return f;
+}
+#ifndef RZ_NUDGE_SIN
+#define RZ_NUDGE_SIN RZ_NUDGE_ULPS
+#endif
+#ifndef RZ_NUDGE_COS
+#define RZ_NUDGE_COS RZ_NUDGE_ULPS
+#endif
+#ifndef RZ_NUDGE_ACOS
+#define RZ_NUDGE_ACOS RZ_NUDGE_ULPS
+#endif
+#ifndef RZ_NUDGE_ASIN
+#define RZ_NUDGE_ASIN RZ_NUDGE_ULPS
+#endif
+#ifndef RZ_NUDGE_ATAN2
+#define RZ_NUDGE_ATAN2 RZ_NUDGE_ULPS
+#endif
+#ifndef RZ_NUDGE_POW
+#define RZ_NUDGE_POW RZ_NUDGE_ULPS
+#endif
+#ifndef RZ_NUDGE_EXP
+#define RZ_NUDGE_EXP RZ_NUDGE_ULPS
+#endif
+#ifndef RZ_NUDGE_LOG
+#define RZ_NUDGE_LOG RZ_NUDGE_ULPS
+#endif
+/* functions, not macros: an argument with a side effect (a draw of the RNG) is evaluated once */
+static inline float rz_sinf(float x) { return rz_nudge(sin((double)x), x, 1.0f, RZ_NUDGE_SIN); }
+static inline float rz_cosf(float x) { return rz_nudge(cos((double)x), x, 2.0f, RZ_NUDGE_COS); }
+static inline float rz_acosf(float x) { return rz_nudge(acos((double)x), x, 3.0f, RZ_NUDGE_ACOS); }
+static inline float rz_asinf(float x) { return rz_nudge(asin((double)x), x, 4.0f, RZ_NUDGE_ASIN); }
+static inline float rz_atan2f(float y, float x) { return rz_nudge(atan2((double)y, (double)x), y, x, RZ_NUDGE_ATAN2); }
+static inline float rz_powf(float x, float y) { return rz_nudge(pow((double)x, (double)y), x, y, RZ_NUDGE_POW); }
+static inline float rz_expf(float x) { return rz_nudge(exp((double)x), x, 5.0f, RZ_NUDGE_EXP); }
+static inline float rz_logf(float x) { return rz_nudge(log((double)x), x, 6.0f, RZ_NUDGE_LOG); }
+#define RZ_SINF(x) rz_sinf(x)
+#define RZ_COSF(x) rz_cosf(x)
+#define RZ_ACOSF(x) rz_acosf(x)
+#define RZ_ASINF(x) rz_asinf(x)
+#define RZ_ATAN2F(y, x) rz_atan2f(y, x)
+#define RZ_POWF(x, y) rz_powf(x, y)
+#define RZ_EXPF(x) rz_expf(x)
+#define RZ_LOGF(x) rz_logf(x)
+const char* rzo_math_mode(void) { return "nudged"; }
+#else
 #define RZ_SINF(x) sinf(x)
 #define RZ_COSF(x) cosf(x)
 #define RZ_ACOSF(x) acosf(x)
@@ -30,6 +97,7 @@
 #define RZ_EXPF(x) expf(x)
 #define RZ_LOGF(x) logf(x)
 const char* rzo_math_mode(void) { return "libm"; }
+#endif
 
 #define RZ_PI 3.14159265358979323846f /* std::numbers::pi_v<float> */
 
@@ -267,7 +335,11 @@ static void transform_g2l(const hiprz_instance* in, ray_t* ray) {
     ray->direction = v3_div(ray->direction, v3_from(in->scale));
 }
 static inline v3 transform_l2g(const hiprz_instance* in, v3 v) {
+#ifdef RZ_MUT_ABS_SCALE /* mutant: normals of a mirrored instance (negative scale) transformed with the scale's magnitude */
+    v = v3_div(v, V3(fabsf(in->scale[0]), fabsf(in->scale[1]), fabsf(in->scale[2])));
+#else
     v = v3_div(v, v3_from(in->scale));
+#endif
     return transform_forward(in->x_axis, in->y_axis, in->z_axis, v);
 }
 static inline v3 transform_l2g_noscale(const hiprz_instance* in, v3 v) {
@@ -361,8 +433,13 @@ static void texel_coords(const hiprz_texture* tex, float u, float v, uint32_t* p
     }
     u *= tex->scale[0];
     v *= tex->scale[1];
+#ifdef RZ_MUT_WRAP_TRUNC /* mutant: a negative coordinate's fraction taken toward zero instead of floored */
+    u = fabsf(fmodf(u, 1.0f));
+    v = 1.0f - fabsf(fmodf(v, 1.0f));
+#else
     u = fmodf(fmodf(u, 1.0f) + 1.0f, 1.0f);
     v = 1.0f - fmodf(fmodf(v, 1.0f) + 1.0f, 1.0f);
+#endif
     uint32_t x = (uint32_t)(u * (float)tex->width);
     uint32_t y = (uint32_t)(v * (float)tex->height);
     if (x > tex->width - 1u) x = tex->width - 1u;
@@ -446,7 +523,14 @@ static void analyze_intersection(const kctx* k, const traversal_t* tr, surface_t
 
     /* instance.material(id): m_materials[min(id, 63)], unset -> default material */
     uint32_t mat_slot = tri->material_flags & HIPRZ_TRI_MATERIAL_MASK;
+#if defined(RZ_MUT_SLOT_WRAP) /* mutant: a material id beyond 63 wraps instead of clamping */
+    mat_slot &= 63u;
+#elif defined(RZ_MUT_SLOT_LAST) /* mutant: an id beyond the instance's slots takes the last slot instead of the default material */
     if (mat_slot > 63u) mat_slot = 63u;
+    if (in->material_count && mat_slot >= in->material_count) mat_slot = in->material_count - 1u;
+#else
+    if (mat_slot > 63u) mat_slot = 63u;
+#endif
     int32_t mat = -1;
     if (mat_slot < in->material_count) mat = s->inst_materials[in->material_base + mat_slot];
     sf->surface_material = mat < 0 ? HIPRZ_MATERIAL_DEFAULT : (uint32_t)mat;
@@ -495,7 +579,15 @@ static int closest_intersection(const kctx* k, ray_t* ray, surface_t* sf, traver
     if (s->n_instances == 0) return 0;
     const hiprz_node* root = &s->nodes[s->tlas_root];
     COUNT(k, box_tests, 1);
-    if (!box_hit(root->bb_min, root->bb_max, ray)) return 0;
+    if (!box_hit(root->bb_min, root->bb_max, ray)) {
+#ifdef RZ_MUT_SKY_UV /* mutant: the sky's texcrd also where the ray misses the world's root box (the CPU engine keeps (0, 0) there) */
+        if (sf) {
+            sf->u = -(0.5f + (RZ_ATAN2F(ray->direction.z, ray->direction.x) / (RZ_PI * 2.0f)));
+            sf->v = 0.5f + (RZ_ASINF(ray->direction.y) / RZ_PI);
+        }
+#endif
+        return 0;
+    }
 
     traverse_world(k, s->tlas_root, ray, &tr);
     if (tr_out) *tr_out = tr;
@@ -883,6 +975,13 @@ static float fresnel_specular_ratio(v3 vN, v3 vI, float n1, float n2, float* fx,
     const float ratio = n1 / n2;
     const float cosi = fabsf(v3_dot(vI, vN));
     const float sin2_t = ratio * ratio * (1.0f - cosi * cosi);
+#ifdef RZ_MUT_IOR_ONE /* mutant: the ratio of two equal indices taken through an approximate reciprocal: ior 1 in ior 1 bends the ray */
+    if (n1 == n2) {
+        *fx = 1.0f - 0x1p-11f;
+        *fy = *fx * cosi - sqrtf(1.0f - *fx * *fx * (1.0f - cosi * cosi));
+        return 0.0f;
+    }
+#endif
     if (sin2_t >= 1.0f) return 1.0f;
     const float cost = sqrtf(1.0f - sin2_t);
     const float Rp = ((n1 * cosi) - (n2 * cost)) / ((n1 * cosi) + (n2 * cost));
@@ -1093,7 +1192,11 @@ static col spot_light_sampling(const kctx* k, const ray_t* ray, v3 point, v3 nex
         const float solid_angle = A / (d1 * d1);
         const float sctr_factor = RZ_EXPF(-dPL * s->materials[ray->material].scattering);
 
+#ifdef RZ_MUT_SPOT_ANGLE /* mutant: the cone test against the beam angle instead of its cosine */
+        const float beam = (float)(light->angle < v3_similarity(v3_neg(vPL), v3_from(light->direction)));
+#else
         const float beam = (float)(light->cos_angle < v3_similarity(v3_neg(vPL), v3_from(light->direction)));
+#endif
         if (beam < 1.0e-4f) continue;
 
         const float L_pdf = 1.0f / solid_angle;

@@ -16,6 +16,10 @@
  * the missing headers (vector normalise / similarity / rotate, ColorF arithmetic,
  * Color->ColorF) it follows the reference's own CUDA restatement of the same types
  * (RayZath/cuda_render_parts.cuh:15-330, 520-700).  See DESIGN.md §Oracle.
+ *
+ * The Makefile also compiles this file into libm stand-ins (-DRZ_NUDGE_ULPS: every inexact libm
+ * result moved n ulps) and mutants (-DRZ_MUT_<NAME>: one deliberate rare-case bug each) for the
+ * lockstep comparison of tests/lockstep.py; the same rule holds for them.
  */
 #ifndef RZ_ORACLE_H
 #define RZ_ORACLE_H

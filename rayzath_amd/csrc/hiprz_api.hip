@@ -845,7 +845,11 @@ std::vector<unsigned char> graph_key_of(hiprz_ctx* c, const DFrame& f, uint32_t 
 
 int render_passes(hiprz_ctx* c, uint32_t n_passes, bool counted) {
     if (!c->have_scene || !c->have_camera) return fail(c, HIPRZ_ERR_STATE, "render before scene and camera upload");
-    if (n_passes == 0 || c->n_local_tiles == 0) return HIPRZ_OK;
+    if (n_passes == 0) return HIPRZ_OK;
+    if (c->n_local_tiles == 0) {  // a part that owns no tile of this frame traces nothing: its ray counter restarts with the frame all the same
+        if (c->reset_pending) c->ray_count = 0;  // (it held the previous frame's rays, which hiprz_ray_count would go on adding to the other parts')
+        return HIPRZ_OK;
+    }
     resolve_pipeline(c);  // the choice depends on the selected camera's shard size too
     StageTimer timer;
     if (defer_shadows(c)) {  // hand-over buffers of the deferred shadow rays: (4 + 2 * samples) float4 per owned pixel

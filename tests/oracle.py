@@ -23,6 +23,14 @@ class _Ctx(C.Structure):
 
 
 _lib = None
+_variants = {}
+
+
+def variant(name):
+    """oracle/librz_oracle_<name>.so: a libm stand-in (lo, hi, mix, lo2, hi2, mix2) or a mutant (mut_<bug>), see oracle/Makefile."""
+    if name not in _variants:
+        _variants[name] = load(os.path.join(ROOT, "oracle", f"librz_oracle_{name}.so"))
+    return _variants[name]
 
 
 def load(path=LIB_PATH):
@@ -92,6 +100,25 @@ class OracleRenderer:
                 for k, v in cnt.as_dict().items():
                     total[k] += v
         return total
+
+    def adopt(self, accum, state, passes):
+        """Continue from another renderer's frame: its accumulator (H, W, 4), its path state (the dict of `state` / Context.read_state)
+        and its pass count replace this context's.  The ray colour's alpha is not part of the exported state and is never read: 1."""
+        c, n = self.ctx.contents, self.w * self.h
+
+        def put(ptr, values, dtype, width):
+            flat = np.ascontiguousarray(values, dtype=dtype).reshape(n * width)
+            C.memmove(ptr, flat.ctypes.data, flat.nbytes)
+
+        put(c.image, accum, np.float32, 4)
+        put(c.ray_origin, state["origin"], np.float32, 3)
+        put(c.ray_direction, state["direction"], np.float32, 3)
+        color = np.ones((self.h, self.w, 4), np.float32)
+        color[..., :3] = state["color"]
+        put(c.ray_color, color, np.float32, 4)
+        put(c.ray_material, state["material"], np.uint32, 1)
+        put(c.path_depth, state["depth"], np.uint8, 1)
+        c.passes = int(passes)
 
     def _arr(self, ptr, shape, dtype):
         n = int(np.prod(shape))
