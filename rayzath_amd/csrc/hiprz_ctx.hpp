@@ -1,11 +1,13 @@
 // hiprz_ctx.hpp — host-side state of a context (struct hiprz_ctx) and what the translation units of libhiprz.so share:
-// hiprz_api.hip (the C-ABI, scene upload, readback), hiprz_launch_trace.hip / hiprz_launch_shade.hip / hiprz_launch_batch.hip
-// (the pass kernels' instantiations and their launch logic) and hiprz_sort.hip (ray reordering).
+// hiprz_api.hip (context life cycle, scene upload and updates, settings, the render loop), hiprz_readback.hip (parts -> frame: tone map,
+// assembly, reads, tile export, present), hiprz_launch_*.hip (the pass kernels' instantiations and their launch logic), hiprz_sort.hip
+// (ray reordering), hiprz_build.hip (trees built on the device) and hiprz_denoise.hip (denoising).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -78,6 +80,25 @@ struct DeviceArray {
         ptr = nullptr;
         count = 0;
     }
+};
+
+// Multi-part head: a buffer its peers push their tile-major buffers into, each on ITS stream, before kernels on the head's stream read them
+// (push_part, mark_consumed below).  `consumed`: recorded on the head's stream behind the last launch that reads `buf`; a peer's next push,
+// whose stream runs ahead of the head's, waits for it.  The event belongs to the buffer, whoever pushes and whoever reads.
+struct PartStaging {
+    DeviceArray<uint8_t> buf;
+    hipEvent_t consumed = nullptr;
+    bool recorded = false;
+    void release() {
+        buf.release();
+        if (consumed) (void)hipEventDestroy(consumed);
+        consumed = nullptr, recorded = false;
+    }
+};
+struct PartCopy {  // one copy of a push
+    void* dst;
+    const void* src;
+    size_t bytes;
 };
 
 }  // namespace hiprz
@@ -155,7 +176,7 @@ struct hiprz_frame_state {
     bool frame_started = false;   // a first pass ran since the frame buffers were (re)allocated
     bool history_ready = false;   // prev_accum / prev_depth already hold the whole previous frame (a multi-device head assembled it)
     float temporal_blend = 0.75f;
-    hiprz::DeviceArray<uint8_t> gather;  // multi-device head: the peers' tile buffers land here before one launch untiles them all
+    hiprz::PartStaging gather;  // multi-device head: the parts' tile buffers land here (slice 0: the head's own) before one launch reads them all
     hiprz::DeviceArray<float4> sum_accum;  // HIPRZ_SHARD_SAMPLES head: the parts' accumulators summed, tile-major like `accum`
     // hiprz_present: two frame slots per camera, each `rgba8 | depth | 16-byte ray-cast record` on the device and as pinned host memory,
     // allocated when the camera is uploaded at a new size (allocate_present), never by a present
@@ -200,19 +221,12 @@ struct hiprz_ctx : hiprz_frame_state {
     hipEvent_t history_done = nullptr;  // head side: the assembled history of a restarted frame has reached every peer
     uint32_t user_rank = 0, user_world = 1;  // hiprz_set_shard as the caller sees it; peers refine it: (rank * n + r, world * n)
     uint32_t shard_mode = 0;          // HIPRZ_SHARD_TILES | HIPRZ_SHARD_SAMPLES (head): how the parts divide the context's share
-    hipEvent_t sum_done = nullptr;    // head, sample mode: the last sum of the parts has read the staging slices (the peers' next copies wait for it)
-    bool sum_recorded = false;
     bool is_peer = false;             // a part of a multi-device context: presents nothing, owns no frame slots
     // hiprz_present: the copy stream moves assembled frame slots to the host beside the render stream; a multi-part head's peers push
-    // their tiles into present_gather, and their next push waits for present_consumed (the present kernel has read the slices)
+    // their tiles into present_gather (slices from peer 1 on).  A staging of its own beside `gather`: a present never allocates
+    // (size_present_gather sizes it when the camera is uploaded), and one may be in flight while a synchronous read uses `gather`.
     hipStream_t copy_stream = nullptr;
-    hiprz::DeviceArray<uint8_t> present_gather;
-    hipEvent_t present_consumed = nullptr;
-    bool consumed_recorded = false;
-    // head, tile mode: the untile kernel of the last frame assembly has read the peers' slices of `gather` (assemble_untiled enqueues only
-    // when the denoiser calls it: a peer's next push into `gather` waits for this, the pattern of present_consumed and sum_done)
-    hipEvent_t gather_consumed = nullptr;
-    bool gather_recorded = false;
+    hiprz::PartStaging present_gather;
 
     // denoising: the filter's ping-pong iterates (shared by the cameras, sized for the largest), hiprz_set_denoise
     hiprz::DeviceArray<float4> dn_tmp[2];
@@ -311,6 +325,11 @@ struct hiprz_ctx : hiprz_frame_state {
 namespace hiprz {
 
 int fail(hiprz_ctx* ctx, int code, const std::string& msg);
+inline uint64_t total_ray_count(const hiprz_ctx* c) {  // hiprz_ray_count: the parts' counters add up to the context's
+    uint64_t n = c->ray_count;
+    for (const hiprz_ctx* p : c->peers) n += p->ray_count;
+    return n;
+}
 // accumulation restarts (or may): the guides of every camera belong to the accumulation that ends here
 inline void stale_guides(hiprz_ctx* c) {
     c->guides_valid = false;
@@ -345,6 +364,46 @@ const bool LaunchSite<Kernel>::registered = (register_kernel(reinterpret_cast<co
         if (rz_e != hipSuccess)                                                                                 \
             return hiprz::fail(ctx, HIPRZ_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(rz_e));    \
     } while (0)
+
+// Multi-device contexts (hiprz_create_multi): a call on the head is repeated on every peer first; a peer's failure is the call's.
+#define RZ_FANOUT(c, call)                                                                                                     \
+    for (hiprz_ctx* p : (c)->peers) {                                                                                         \
+        const int rz_rc = (call);                                                                                             \
+        if (rz_rc != HIPRZ_OK) return hiprz::fail(c, rz_rc, "device " + std::to_string(p->device) + ": " + p->error);       \
+    }
+
+// ---- multi-part heads: the slices of the parts' tile-major buffers, and how they reach the head ----
+struct PartGeometry {
+    uint32_t n_parts;  // the head and its peers
+    size_t stride;     // pixels per slice of a staging: the head's own share — it owns the lowest rank of the context, no part has more tiles
+    size_t capacity;   // pixels per slice handed OUT (hiprz_export_*_tiles): the largest sub-shard of the job, whose lowest ranks own one tile more
+};                     // (c->world is already user_world * parts on a multi-part head)
+inline PartGeometry part_geometry(const hiprz_ctx* c) {
+    const size_t own = size_t(c->n_local_tiles) * 256u;
+    return {uint32_t(c->peers.size()) + 1u, own, c->peers.empty() ? own : size_t(shard_local_tiles(c->tiles_x, c->tiles_y, 0u, c->world)) * 256u};
+}
+// `peer` copies into the head's memory on ITS stream, behind its own rendering (peer-to-peer over xGMI from another device) and behind the
+// last reader of `staging` (null: the destination is no staging, hiprz_export_*_tiles); the head's stream waits for the copies.  Nothing
+// here synchronises with the host.  A peer with nothing to copy is skipped.
+inline int push_part(hiprz_ctx* head, hiprz_ctx* peer, const PartStaging* staging, std::initializer_list<PartCopy> copies) {
+    size_t bytes = 0;
+    for (const PartCopy& k : copies) bytes += k.bytes;
+    if (!bytes) return HIPRZ_OK;
+    (void)hipSetDevice(peer->device);
+    if (staging && staging->recorded) RZ_HIP(head, hipStreamWaitEvent(peer->stream, staging->consumed, 0));
+    for (const PartCopy& k : copies) RZ_HIP(head, hipMemcpyPeerAsync(k.dst, head->device, k.src, peer->device, k.bytes, peer->stream));
+    RZ_HIP(head, hipEventRecord(peer->peer_done, peer->stream));
+    (void)hipSetDevice(head->device);
+    RZ_HIP(head, hipStreamWaitEvent(head->stream, peer->peer_done, 0));
+    return HIPRZ_OK;
+}
+// behind the last launch on the head's stream that reads `staging`: what the next push into it waits for
+inline int mark_consumed(hiprz_ctx* head, PartStaging& staging) {
+    if (!staging.consumed) RZ_HIP(head, hipEventCreateWithFlags(&staging.consumed, hipEventDisableTiming));
+    RZ_HIP(head, hipEventRecord(staging.consumed, head->stream));
+    staging.recorded = true;
+    return HIPRZ_OK;
+}
 
 constexpr uint32_t kLatencyBoundNodes = 32768u;  // trees beyond ~1 MiB of nodes: fetches come from L2 / HBM, occupancy hides them
 constexpr uint32_t kTopCacheNodes = 682u;        // 682 x 36 B = 24 KiB per workgroup: ~9 levels of every tree, 5 workgroups per CU
@@ -396,12 +455,19 @@ uint32_t device_build_regions(std::vector<DeviceMesh>& meshes, uint32_t first_fr
 int device_build_mesh_trees(hiprz_ctx* c, std::vector<DeviceMesh>& meshes, const std::vector<uint32_t>& instance_mesh, bool validate);
 int device_build_world_tree(hiprz_ctx* c, bool validate);
 int device_update_triangles(hiprz_ctx* c, uint32_t first, uint32_t n, const hiprz_tri* tris, const hiprz_tri_attr* attrs);
-// the selected camera's accumulator as hiprz_read_accum defines it, assembled row-major in c->image_f4 on the context's stream (hiprz_api.hip)
+// parts -> frame (hiprz_readback.hip).  The frame a restart replaces, for HIPRZ_COMPAT_REPROJECTION: before a first pass (keep_history),
+// on a multi-part head before the render call fans out (assemble_history); hiprz_present's frame slots and staging
+bool keep_history(hiprz_ctx* c);
+int assemble_history(hiprz_ctx* c);
+void release_present(hiprz_ctx* c, hiprz_frame_state* f);
+int size_present_gather(hiprz_ctx* c);
+int allocate_present(hiprz_ctx* c);
+// the selected camera's accumulator as hiprz_read_accum defines it, assembled row-major in c->image_f4 on the context's stream
 int assemble_accum_image(hiprz_ctx* c);
 // denoising: rz_guide_kernel into c->guides when they are stale (hiprz_launch_guide.hip); the filter on `stream` (hiprz_denoise.hip)
 int ensure_guides(hiprz_ctx* c);
 int denoise_frame(hiprz_ctx* c, const hiprz_denoise_params* params, uint32_t* rgba8_out);
-// the selected camera's variance estimate as hiprz_read_variance defines it, row-major in c->var_image on the context's stream (hiprz_api.hip)
+// the selected camera's variance estimate as hiprz_read_variance defines it, row-major in c->var_image on the context's stream
 int assemble_variance_image(hiprz_ctx* c);
 int sort_workspace(hiprz_ctx* c, size_t n);  // (re)allocates the sort's buffers for n keys
 int sort_temp_resize(hiprz_ctx* c, hiprz_frame_state::SortTemp& t, size_t n);

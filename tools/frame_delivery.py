@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""What it costs to hand every frame to the host: bench.py's protocol (one context, one stream, renderFirstPass, warm-up, then timed
+"""What it costs to hand every frame to the host: bench.py's protocol (one context, one stream — or, with --streams N, the frame's tiles
+over N streams of GPU 0, whose present goes through the head's staging —, renderFirstPass, warm-up, then timed
 rounds of exactly --steps steps of 8 passes between sync fences, the loops alternating from round to round, median per loop) for
 
   render     render(8) + tone map                                            bench's `value`
@@ -19,7 +20,7 @@ sys.path.insert(0, ROOT)
 RPP = 8
 
 
-def measure(config, steps, warmup, rounds):
+def measure(config, steps, warmup, rounds, streams=1):
     from rayzath_amd import scenes
     from rayzath_amd.engine import TREE_AUTO, Context, RenderConfig, Tracing
     from rayzath_amd.scene import camera_struct, flatten
@@ -29,7 +30,7 @@ def measure(config, steps, warmup, rounds):
     flat, cam = flatten(world), camera_struct(world.camera)
     W, H = cam.width, cam.height
     x, y = W // 2, H // 2
-    ctx = Context(0)
+    ctx = Context([0] * streams if streams > 1 else 0)
     ctx.set_tree(TREE_AUTO)
     ctx.upload_scene(flat)
     ctx.upload_camera(cam)
@@ -83,10 +84,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--streams", type=int, default=1, help="contexts-with-a-stream on GPU 0 that share the frame (hiprz_create_multi)")
     ap.add_argument("--out")
     args = ap.parse_args()
-    result = {"protocol": f"{args.rounds} alternating rounds of {args.steps} steps x {RPP} passes per loop, median round; one context, one stream",
-              "configs": {c: measure(c, args.steps, args.warmup, args.rounds) for c in args.configs.split(",")}}
+    result = {"protocol": f"{args.rounds} alternating rounds of {args.steps} steps x {RPP} passes per loop, median round; one context, {args.streams} stream(s)",
+              "configs": {c: measure(c, args.steps, args.warmup, args.rounds, args.streams) for c in args.configs.split(",")}}
     text = json.dumps(result, indent=1)
     print(text)
     if args.out:
