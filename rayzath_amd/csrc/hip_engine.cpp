@@ -1,5 +1,5 @@
 // hip_engine.cpp — see hip_engine.hpp.  Host-only C++ (no device code): everything below the
-// C-ABI lives in hiprz_api.hip / hiprz_readback.hip / hiprz_host.cpp.
+// C-ABI lives in hiprz_api.hip / hiprz_scene.hip / hiprz_readback.hip / hiprz_host.cpp / hiprz_scene_host.cpp.
 #include "hip_engine.hpp"
 
 #include <algorithm>

@@ -1,9 +1,10 @@
-// hiprz_api.hip — the device half of the C-ABI declared in include/hiprz.h: context life cycle, scene mirroring, settings, render calls.
+// hiprz_api.hip — the device half of the C-ABI declared in include/hiprz.h: context life cycle, settings, render calls.
 //
 // Replaces, for the HIPGPU backend, what the reference's CUDA backend does in cuda_engine_core.cu (host<->device
 // mirroring), cuda_engine_renderer.cu (launch sequence) and cuda_postprocess_kernel.cu (pass update).
-// The pass kernels live in hiprz_kernels.hpp and are instantiated by hiprz_launch_*.hip; what turns the parts' tiles into frames (tone
-// map, assembly, reads, export, present) lives in hiprz_readback.hip.
+// The pass kernels live in hiprz_kernels.hpp and are instantiated by hiprz_launch_*.hip; scene mirroring lives in hiprz_scene.hip (and,
+// where it needs no device, hiprz_scene_host.cpp); what turns the parts' tiles into frames (tone map, assembly, reads, export, present)
+// lives in hiprz_readback.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -161,74 +162,7 @@ void invalidate_graphs(hiprz_ctx* c) {
 }
 }  // namespace hiprz
 
-// Scene calls: a peer on ANOTHER device mirrors the scene itself; a peer on the head's own device (a second stream on the same GPU)
-// walks the head's copy — one scene blob per device, however many streams share it.
-#define RZ_FANOUT_OTHER_DEVICES(c, call)                                                                                       \
-    for (hiprz_ctx* p : (c)->peers) {                                                                                         \
-        if (p->device == (c)->device) continue;                                                                               \
-        const int rz_rc = (call);                                                                                             \
-        if (rz_rc != HIPRZ_OK) return fail(c, rz_rc, "device " + std::to_string(p->device) + ": " + p->error);              \
-    }
-
 namespace {
-
-// a same-device peer takes over the head's view of the scene (pointers into the head's buffers, every derived figure)
-void adopt_scene(hiprz_ctx* p, const hiprz_ctx* head) {
-    p->dscene = head->dscene, p->have_scene = head->have_scene, p->stack_entries = head->stack_entries, p->lds_scene = head->lds_scene;
-    p->n_nodes = head->n_nodes, p->flat_world = head->flat_world, p->n_textures = head->n_textures, p->scene_tree = head->scene_tree;
-    p->tree_mode = head->tree_mode, p->device_sah = head->device_sah, p->build_sah = head->build_sah, p->n_tris = head->n_tris, p->n_tlas_order = head->n_tlas_order;
-    p->scene_shared = true;
-    invalidate_graphs(p);
-    p->reset_pending = true;
-    for (auto& f : p->parked) f.reset_pending = true;
-}
-void share_scene_with_streams(hiprz_ctx* c) {
-    for (hiprz_ctx* p : c->peers)
-        if (p->device == c->device) adopt_scene(p, c);
-}
-
-struct TreeCheck {
-    const hiprz_scene* sc;
-    std::vector<uint32_t>& skip;
-    std::vector<uint8_t> visited;
-    uint32_t max_depth = 0;
-    std::string error;
-    std::vector<uint32_t> world_leaves;
-
-    // Walks one tree from `root`, verifies every index it will make the kernel follow, fills
-    // the skip links, returns false on the first violation.  `is_world`: leaves index tlas_order.
-    bool walk(uint32_t root, bool is_world) {
-        struct Item {
-            uint32_t node, skip, depth;
-        };
-        std::vector<Item> stack{{root, RZ_END, 1u}};
-        while (!stack.empty()) {
-            const Item it = stack.back();
-            stack.pop_back();
-            if (it.node >= sc->n_nodes) return err("node index out of range");
-            if (visited[it.node]) return err("node reachable twice (trees must be disjoint and acyclic)");
-            visited[it.node] = 1;
-            skip[it.node] = it.skip;
-            if (it.depth > max_depth) max_depth = it.depth;
-            if (it.depth > 64u) return err("tree deeper than 64 levels");
-            const hiprz_node& n = sc->nodes[it.node];
-            if (n.meta & HIPRZ_NODE_LEAF) {
-                const uint64_t end = uint64_t(n.begin) + (n.meta & HIPRZ_NODE_COUNT_MASK);
-                if (end > (is_world ? sc->n_tlas_order : sc->n_tris)) return err("leaf range out of bounds");
-                if (is_world) world_leaves.push_back(it.node);
-            } else {
-                if (uint64_t(n.begin) + 1 >= sc->n_nodes) return err("child index out of range");
-                stack.push_back({n.begin + 1, it.skip, it.depth + 1});
-                stack.push_back({n.begin, n.begin + 1, it.depth + 1});
-            }
-        }
-        return true;
-    }
-    bool err(const char* m) {
-        error = m;
-        return false;
-    }
-};
 
 void release_variance(hiprz_frame_state* c) {
     c->var_snap.release(), c->var_m0.release(), c->var_m1.release(), c->var_tiles.release(), c->var_image.release(), c->sum_m0.release(), c->sum_m1.release();
@@ -729,202 +663,6 @@ int render_impl(hiprz_ctx* c, uint32_t n_passes, bool counted) {
     return HIPRZ_OK;
 }
 
-// Everything the kernels will dereference is checked here, on the host, before any launch: a
-// bad index or a cyclic tree would otherwise fault or hang the GPU.  Also derives the skip links,
-// the world-tree leaves and the tree depths the upload needs.
-struct SceneCheck {
-    std::string error;
-    std::vector<uint8_t> reachable;  // nodes some walk can get to (a snapshot may hold others: they are never followed)
-    std::vector<uint32_t> skip;
-    std::vector<uint32_t> world_leaves;
-    uint32_t world_depth = 0, mesh_depth = 0;
-};
-int check_scene(const hiprz_scene* sc, SceneCheck& out) {
-    auto bad = [&out](const std::string& m) {
-        out.error = m;
-        return HIPRZ_ERR_INVALID;
-    };
-    if (!sc) return bad("scene is null");
-    // ---- validate everything the kernels will dereference, on the host, before any launch ----
-    if (sc->n_materials < 2 || !sc->materials) return bad("scene needs materials[0]=world, [1]=default");
-    if (sc->n_materials > 65536u) return bad("more than 65536 materials");
-    if ((sc->n_nodes && !sc->nodes) || (sc->n_tris && (!sc->tris || !sc->tri_attrs)) || (sc->n_instances && !sc->instances) ||
-        (sc->n_tlas_order && !sc->tlas_order) || (sc->n_inst_materials && !sc->inst_materials) ||
-        (sc->n_textures && !sc->textures) || (sc->texel_bytes && !sc->texels) || (sc->n_spot_lights && !sc->spot_lights) ||
-        (sc->n_direct_lights && !sc->direct_lights))
-        return bad("upload_scene: null array with non-zero count");
-    for (uint32_t i = 0; i < sc->n_textures; ++i) {
-        const hiprz_texture& t = sc->textures[i];
-        const uint64_t texel = t.kind == HIPRZ_TEX_R8 ? 1u : 4u;
-        if (t.kind > HIPRZ_TEX_R32F || t.width == 0 || t.height == 0 || (t.offset & 3u) ||
-            uint64_t(t.offset) + texel * t.width * t.height > sc->texel_bytes)
-            return bad("texture " + std::to_string(i) + ": bad kind/size/offset");
-    }
-    auto tex_ok = [&](int32_t t, uint32_t kind) { return t < 0 || (uint32_t(t) < sc->n_textures && sc->textures[t].kind == kind); };
-    for (uint32_t i = 0; i < sc->n_materials; ++i) {
-        const hiprz_material& m = sc->materials[i];
-        if (!tex_ok(m.texture, HIPRZ_TEX_RGBA8) || !tex_ok(m.normal_map, HIPRZ_TEX_RGBA8) ||
-            !tex_ok(m.metalness_map, HIPRZ_TEX_R8) || !tex_ok(m.roughness_map, HIPRZ_TEX_R8) ||
-            !tex_ok(m.emission_map, HIPRZ_TEX_R32F))
-            return bad("material " + std::to_string(i) + ": map index/kind invalid");
-    }
-    for (uint32_t i = 0; i < sc->n_inst_materials; ++i)
-        if (sc->inst_materials[i] >= int32_t(sc->n_materials))
-            return bad("inst_materials[" + std::to_string(i) + "] out of range");
-    for (uint32_t i = 0; i < sc->n_tlas_order; ++i)
-        if (sc->tlas_order[i] >= sc->n_instances) return bad("tlas_order entry out of range");
-    for (uint32_t i = 0; i < sc->n_instances; ++i) {
-        const hiprz_instance& in = sc->instances[i];
-        if (in.material_count > 64u || uint64_t(in.material_base) + in.material_count > sc->n_inst_materials)
-            return bad("instance " + std::to_string(i) + ": material table out of range");
-    }
-    std::vector<uint32_t> skip(sc->n_nodes ? sc->n_nodes : 1, RZ_END);
-    TreeCheck check{sc, skip, std::vector<uint8_t>(sc->n_nodes ? sc->n_nodes : 1, 0)};
-    uint32_t world_depth = 0, mesh_depth = 0;
-    if (sc->n_instances) {
-        if (!check.walk(sc->tlas_root, true)) return bad("world tree: " + check.error);
-        world_depth = check.max_depth;
-        std::vector<uint8_t> root_seen(sc->n_nodes, 0);
-        for (uint32_t i = 0; i < sc->n_tlas_order; ++i) {
-            const uint32_t root = sc->instances[sc->tlas_order[i]].blas_root;
-            if (root >= sc->n_nodes) return bad("instance mesh root out of range");
-            if (root_seen[root]) continue;
-            root_seen[root] = 1;
-            check.max_depth = 0;
-            if (!check.walk(root, false)) return bad("mesh tree: " + check.error);
-            mesh_depth = std::max(mesh_depth, check.max_depth);
-        }
-    }
-    out.skip = std::move(skip);
-    out.reachable = std::move(check.visited);
-    out.world_leaves = std::move(check.world_leaves);
-    out.world_depth = world_depth, out.mesh_depth = mesh_depth;
-    return HIPRZ_OK;
-}
-
-// Device-side tables derived from a validated scene (pure host): relayouted nodes + links (reference order and per octant).
-struct DerivedTables {
-    std::vector<uint32_t> new_index;
-    std::vector<hiprz_node> dnodes;
-    std::vector<uint32_t> dskip;
-    std::vector<uint32_t> dskip8;  // [node][octant]: skip links of the front-to-back mesh walk (hiprz_device.hpp: fetch_node_ordered)
-};
-int derive_tables(const hiprz_scene* sc, SceneCheck& chk, DerivedTables& out) {
-    // Relayout: breadth-first over ALL trees at once (world root, then every distinct mesh root, then their child
-    // pairs, ...), children staying adjacent.  The levels nearest the roots become a prefix of the array (the part
-    // MODE 3 caches in LDS) and siblings/cousins share cache lines.  Leaf ranges are untouched.
-    std::vector<uint32_t>& new_index = out.new_index;
-    new_index.assign(sc->n_nodes, RZ_END);
-    std::vector<uint32_t> bfs;
-    bfs.reserve(sc->n_nodes);
-    auto enqueue = [&](uint32_t old) {
-        if (old < sc->n_nodes && new_index[old] == RZ_END) {
-            new_index[old] = uint32_t(bfs.size());
-            bfs.push_back(old);
-        }
-    };
-    if (sc->n_instances) enqueue(sc->tlas_root);
-    for (uint32_t i = 0; i < sc->n_tlas_order; ++i) enqueue(sc->instances[sc->tlas_order[i]].blas_root);
-    // Child pairs follow the roots.  A 64-byte record pair is one 128-byte cache line when it starts at an even index: one empty slot
-    // behind an odd number of roots puts every pair on a line of its own, so that the second child — visited after the first one's
-    // subtree, or probed together with it — is on the line the first one brought in.
-    const uint32_t pad_at = (bfs.size() & 1u) ? uint32_t(bfs.size()) : RZ_END;
-    if (pad_at != RZ_END) bfs.push_back(RZ_END);
-    for (size_t q = 0; q < bfs.size(); ++q) {
-        if (bfs[q] == RZ_END) continue;
-        const hiprz_node& n = sc->nodes[bfs[q]];
-        if (!(n.meta & HIPRZ_NODE_LEAF)) enqueue(n.begin), enqueue(n.begin + 1);
-    }
-    for (uint32_t old = 0; old < sc->n_nodes; ++old) enqueue(old);  // nodes no instance reaches keep a slot
-    const size_t n_total = bfs.size();  // the scene's nodes + the padding slot
-    std::vector<hiprz_node>& dnodes = out.dnodes;
-    std::vector<uint32_t>& dskip = out.dskip;
-    hiprz_node empty{};
-    empty.meta = HIPRZ_NODE_LEAF;  // no triangles, reached by nothing
-    dnodes.assign(n_total ? n_total : 0, empty);
-    dskip.assign(n_total ? n_total : 1, RZ_END);
-    for (uint32_t old = 0; old < sc->n_nodes; ++old) {
-        hiprz_node n = sc->nodes[old];
-        if (!(n.meta & HIPRZ_NODE_LEAF)) n.begin = new_index[n.begin];
-        dnodes[new_index[old]] = n;
-        dskip[new_index[old]] = chk.skip[old] == RZ_END ? RZ_END : new_index[chk.skip[old]];
-    }
-
-    // ---- skip links per ray octant (front-to-back walk) ----
-    // Under octant o an inner node with partition type p (X=2, Y=1, Z=0) is left towards its SECOND child first when bit p of o is
-    // set; a size split (type 3) is never flipped.  The child visited first links to its sibling, the other one inherits the
-    // parent's link.  Parents precede their children in the breadth-first numbering, so one ascending sweep fills all tables;
-    // roots end their walks (RZ_END).  Octant 0 reproduces dskip.
-    std::vector<uint32_t>& dskip8 = out.dskip8;
-    dskip8.assign((n_total ? n_total : 1) * 8u, RZ_END);
-    for (uint32_t n = 0; n < n_total; ++n) {
-        const hiprz_node& nd = dnodes[n];
-        if (nd.meta & HIPRZ_NODE_LEAF) continue;
-        const uint32_t ptype = (nd.meta >> HIPRZ_NODE_PTYPE_SHIFT) & 3u, c0 = nd.begin;
-        if (c0 <= n || size_t(c0) + 1 >= n_total) continue;  // cannot happen after check_scene + the BFS relayout; keeps the sweep safe
-        for (uint32_t o = 0; o < 8u; ++o) {
-            const uint32_t flip = (o >> ptype) & 1u;  // ptype 3 reads bit 3 = 0
-            dskip8[size_t(c0 + flip) * 8u + o] = c0 + 1u - flip;
-            dskip8[size_t(c0 + 1u - flip) * 8u + o] = dskip8[size_t(n) * 8u + o];
-        }
-    }
-
-    // The kernels follow these derived tables blindly: prove on the host that every walk over them terminates
-    // (each step moves strictly forward in depth-first order, so a walk may take at most one step per node).
-    {
-        auto terminates = [](const std::vector<hiprz_node>& nodes, const std::vector<uint32_t>& links, uint32_t root) {
-            uint32_t n = root;
-            for (size_t steps = 0; steps <= nodes.size(); ++steps) {
-                if (n == RZ_END) return true;
-                if (n >= nodes.size()) return false;
-                const hiprz_node& nd = nodes[n];
-                n = !(nd.meta & HIPRZ_NODE_LEAF) ? nd.begin : links[n];
-            }
-            return false;
-        };
-        bool ok = true;
-        for (uint32_t old = 0; ok && old < sc->n_nodes; ++old)  // the stack walks reach the second child as first + 1
-            if (!(sc->nodes[old].meta & HIPRZ_NODE_LEAF)) ok = new_index[sc->nodes[old].begin + 1] == new_index[sc->nodes[old].begin] + 1u;
-        if (ok && sc->n_instances) ok = terminates(dnodes, dskip, new_index[sc->tlas_root]);
-        for (uint32_t i = 0; ok && i < sc->n_tlas_order; ++i) {
-            const uint32_t root = new_index[sc->instances[sc->tlas_order[i]].blas_root];
-            ok = terminates(dnodes, dskip, root);
-        }
-        // the same for every octant's links: a walk that enters every box takes exactly one step per node of the tree it walks
-        auto terminates8 = [&](uint32_t root, uint32_t o) {
-            uint32_t n = root;
-            for (size_t steps = 0; steps <= dnodes.size(); ++steps) {
-                if (n == RZ_END) return true;
-                if (n >= dnodes.size()) return false;
-                const hiprz_node& nd = dnodes[n];
-                if (!(nd.meta & HIPRZ_NODE_LEAF)) n = nd.begin + ((o >> ((nd.meta >> HIPRZ_NODE_PTYPE_SHIFT) & 3u)) & 1u);
-                else n = dskip8[size_t(n) * 8u + o];
-            }
-            return false;
-        };
-        for (uint32_t old = 0; ok && old < sc->n_nodes; ++old)  // octant 0 is the reference's order (nodes no walk reaches have no links to compare)
-            if (old < chk.reachable.size() && chk.reachable[old]) ok = dskip8[size_t(new_index[old]) * 8u] == dskip[new_index[old]];
-        if (ok && sc->n_instances) ok = terminates8(new_index[sc->tlas_root], 0u);
-        {
-            std::vector<uint8_t> seen(n_total ? n_total : 1, 0);
-            for (uint32_t i = 0; ok && i < sc->n_tlas_order; ++i) {
-                const uint32_t root = new_index[sc->instances[sc->tlas_order[i]].blas_root];
-                if (seen[root]) continue;
-                seen[root] = 1;
-                for (uint32_t o = 0; ok && o < 8u; ++o) ok = terminates8(root, o);
-            }
-        }
-        if (!ok) {
-            chk.error = "internal: derived walk tables are inconsistent (refusing to launch)";
-            return HIPRZ_ERR_INVALID;
-        }
-    }
-    return HIPRZ_OK;
-}
-
-}  // namespace
-
-namespace {
 // hiprz_select_camera on one context: the selected camera's frame state lives in the context itself, the others are parked
 void select_camera_one(hiprz_ctx* c, uint32_t k) {
     if (k == c->active_camera || k >= c->parked.size()) return;
@@ -945,17 +683,6 @@ void assign_setting(hiprz_ctx* c, T& field, const T& value) {
 }  // namespace
 
 extern "C" {
-
-int hiprz_validate_scene(const hiprz_scene* scene, char* message, size_t len) {
-    SceneCheck chk;
-    int rc = check_scene(scene, chk);
-    if (rc == HIPRZ_OK) {  // also prove that the tables the kernels will follow can be derived and terminate
-        DerivedTables derived;
-        rc = derive_tables(scene, chk, derived);
-    }
-    if (message && len) std::snprintf(message, len, "%s", chk.error.c_str());
-    return rc;
-}
 
 int hiprz_create(hiprz_ctx** out, int device_id) {
     if (!out) return fail(nullptr, HIPRZ_ERR_INVALID, "hiprz_create: out is null");
@@ -1118,610 +845,6 @@ int hiprz_destroy(hiprz_ctx* c) {
 }
 
 const char* hiprz_last_error(const hiprz_ctx* c) { return c ? c->error.c_str() : g_create_error.c_str(); }
-
-namespace {
-int build_shadow_world_tree(hiprz_ctx* c, const std::vector<hiprz_instance>& dinst, DScene& d);
-}
-
-int hiprz_upload_scene(hiprz_ctx* c, const hiprz_scene* sc) {
-    if (!c) return HIPRZ_ERR_INVALID;
-    RZ_FANOUT_OTHER_DEVICES(c, hiprz_upload_scene(p, sc));
-    for (hiprz_ctx* p : c->peers)  // streams on this device may still be reading the buffers this call replaces
-        if (p->device == c->device) (void)hipStreamSynchronize(p->stream);
-    struct Share {  // whatever way this call ends, the streams on this device see what the head holds then
-        hiprz_ctx* c;
-        ~Share() {
-            share_scene_with_streams(c);
-            for (hiprz_ctx* p : c->peers)
-                if (p->device == c->device) resolve_pipeline(p);
-        }
-    } share{c};
-    invalidate_graphs(c);
-    StageTimer timer;
-    SceneCheck chk;
-    if (check_scene(sc, chk) != HIPRZ_OK) return fail(c, HIPRZ_ERR_INVALID, "upload_scene: " + chk.error);
-    // opt-in mesh trees of better quality (hiprz_set_tree): the snapshot is rewritten — new nodes, triangles and their attributes in
-    // the new leaf order, every triangle remembering its position in the reference's order — and then takes the usual way
-    hiprz_scene rebuilt_scene;
-    std::vector<hiprz_node> rebuilt_nodes;
-    std::vector<hiprz_tri> rebuilt_tris;
-    std::vector<hiprz_tri_attr> rebuilt_attrs;
-    std::vector<hiprz_instance> rebuilt_instances;
-    uint32_t tree = c->tree_mode;
-    c->build_sah = c->device_sah;
-    if (tree == HIPRZ_TREE_AUTO) {
-        // a scene whose records can be staged in LDS keeps the snapshot's trees (the resident kernels walk those); any other gets the
-        // device's surface-area trees.  (A lower bound of the hot blob: node records, triangles + shading records, instances.)
-        const size_t records = size_t(sc->n_nodes) * 32u + size_t(sc->n_tris) * 144u + size_t(sc->n_instances) * 112u;
-        tree = records > kLdsSceneLimit ? HIPRZ_TREE_DEVICE : HIPRZ_TREE_REFERENCE;
-        c->build_sah = true;
-    }
-    std::vector<uint32_t> order, roots;
-    uint32_t n_nodes = 0u, tlas_root = 0u;
-    bool identity_order = false;
-    if (tree != HIPRZ_TREE_REFERENCE && sc->n_tris != 0u) {
-        const uint32_t max_nodes = sc->n_nodes + 2u * sc->n_tris + sc->n_instances + 1u;
-        rebuilt_nodes.resize(max_nodes);
-        order.resize(sc->n_tris), roots.resize(sc->n_instances ? sc->n_instances : 1u);
-        if (hiprz_rebuild_mesh_trees(sc, tree, rebuilt_nodes.data(), max_nodes, &n_nodes, order.data(), roots.data(), &tlas_root) != HIPRZ_OK) {
-            if (c->tree_mode != HIPRZ_TREE_AUTO)
-                return fail(c, HIPRZ_ERR_INVALID, "upload_scene: the mesh trees could not be rebuilt (leaves of a mesh must tile one range of triangles)");
-            tree = HIPRZ_TREE_REFERENCE;  // HIPRZ_TREE_AUTO promises an upload wherever the snapshot's own trees are valid
-        }
-    }
-    if (tree != HIPRZ_TREE_REFERENCE && sc->n_tris != 0u) {
-        rebuilt_nodes.resize(n_nodes);
-        // (the placeholder trees of a device build keep the snapshot's order when its meshes lie in first-use order, as the hosts'
-        // flatteners lay them out: then the 144 bytes per triangle are not copied, and position i is what triangle i is ranked by)
-        identity_order = true;
-        for (uint32_t i = 0; i < sc->n_tris && identity_order; ++i) identity_order = order[i] == i;
-        if (!identity_order) {
-            rebuilt_tris.resize(sc->n_tris), rebuilt_attrs.resize(sc->n_tris);
-            for (uint32_t i = 0; i < sc->n_tris; ++i) {
-                rebuilt_tris[i] = sc->tris[order[i]];
-                rebuilt_tris[i].pad0 = order[i];
-                rebuilt_attrs[i] = sc->tri_attrs[order[i]];
-            }
-        }
-        rebuilt_instances.assign(sc->instances, sc->instances + sc->n_instances);
-        for (uint32_t i = 0; i < sc->n_instances; ++i) rebuilt_instances[i].blas_root = roots[i];
-        rebuilt_scene = *sc;
-        rebuilt_scene.n_nodes = n_nodes, rebuilt_scene.nodes = rebuilt_nodes.data(), rebuilt_scene.tlas_root = tlas_root;
-        if (!identity_order) rebuilt_scene.tris = rebuilt_tris.data(), rebuilt_scene.tri_attrs = rebuilt_attrs.data();
-        rebuilt_scene.instances = rebuilt_instances.data();
-        sc = &rebuilt_scene;
-        if (check_scene(sc, chk) != HIPRZ_OK) return fail(c, HIPRZ_ERR_INVALID, "upload_scene: rebuilt trees: " + chk.error);
-        c->timings.set("rebuild mesh trees", timer.ms());
-    }
-    const bool own_trees = sc == &rebuilt_scene;
-    const uint32_t world_depth = chk.world_depth, mesh_depth = chk.mesh_depth;
-
-    DerivedTables derived;
-    if (derive_tables(sc, chk, derived) != HIPRZ_OK) return fail(c, HIPRZ_ERR_INVALID, "upload_scene: " + chk.error);
-    // from here on the device buffers of the previous scene are being replaced: until the new one is complete there is no scene
-    // (a failed upload must not leave the old scene's kernels arguments pointing at reallocated buffers)
-    c->have_scene = false;
-    c->stack_entries = world_depth + mesh_depth + 2u;
-    c->dscene.world_stack_entries = world_depth + 1u;
-    c->dscene.mesh_stack_entries = mesh_depth + 1u;
-    std::vector<uint32_t>& new_index = derived.new_index;
-    std::vector<hiprz_node>& dnodes = derived.dnodes;
-    std::vector<uint32_t>& dskip = derived.dskip;
-    // shared-reciprocal division is exact only for coordinates that are 0 or in [2^-60, 2^40)
-    auto coord_ok = [](float x) {
-        uint32_t b;
-        std::memcpy(&b, &x, 4);
-        const uint32_t e = (b >> 23) & 0xFFu;
-        return (b & 0x7FFFFFFFu) == 0u || (e >= 127u - 60u && e < 127u + 40u);
-    };
-    bool fast_div = true;
-    for (const auto& n : dnodes)
-        for (int a = 0; a < 3; ++a) fast_div = fast_div && coord_ok(n.bb_min[a]) && coord_ok(n.bb_max[a]);
-    for (uint32_t i = 0; i < sc->n_instances; ++i)
-        for (int a = 0; a < 3; ++a) fast_div = fast_div && coord_ok(sc->instances[i].bb_min[a]) && coord_ok(sc->instances[i].bb_max[a]);
-
-    (void)hipSetDevice(c->device);
-    // hot blob: one buffer, 16-B aligned sections
-    std::vector<uint8_t> blob;
-    auto append = [&blob](const void* src, size_t bytes) {
-        const uint32_t off = uint32_t(blob.size());
-        blob.resize(blob.size() + ((bytes + 15u) & ~size_t(15)), 0);
-        if (bytes) std::memcpy(blob.data() + off, src, bytes);
-        return off;
-    };
-    DScene& d = c->dscene;
-    // device copies keep every box interleaved, (min.x, max.x, min.y, max.y, min.z, max.z), so one axis' two
-    // plane distances are one packed operand of the box test (hiprz_device.hpp: box_hit)
-    auto interleave = [](float* mn, float* mx) {
-        const float v[6] = {mn[0], mx[0], mn[1], mx[1], mn[2], mx[2]};
-        mn[0] = v[0], mn[1] = v[1], mn[2] = v[2], mx[0] = v[3], mx[1] = v[4], mx[2] = v[5];
-    };
-    for (auto& n : dnodes) interleave(n.bb_min, n.bb_max);  // bb_min[3] and bb_max[3] are contiguous
-    std::vector<hiprz_instance> dinstances(sc->instances, sc->instances + sc->n_instances);
-    for (auto& in : dinstances) {
-        if (in.blas_root < sc->n_nodes) in.blas_root = new_index[in.blas_root];
-        in.pad0 = (in.scale[0] == 1.0f && in.scale[1] == 1.0f && in.scale[2] == 1.0f) ? 1u : 0u;  // x / 1.0f == x: the walk skips it
-        const float v[6] = {in.bb_min[0], in.bb_max[0], in.bb_min[1], in.bb_max[1], in.bb_min[2], in.bb_max[2]};
-        in.bb_min[0] = v[0], in.bb_min[1] = v[1], in.bb_min[2] = v[2];
-        std::memcpy(&in.pad2, &v[3], 4);
-        in.bb_max[0] = v[4], in.bb_max[1] = v[5], in.bb_max[2] = 0.0f;
-    }
-    d.off_nodes = append(dnodes.data(), sizeof(hiprz_node) * dnodes.size());
-    d.off_tlas_order = append(sc->tlas_order, sizeof(uint32_t) * sc->n_tlas_order);
-    d.off_instances = append(dinstances.data(), sizeof(hiprz_instance) * dinstances.size());
-    // device triangles hold v1 and the edges v2 - v1, v3 - v1; v2 and v3 themselves (normal mapping only) move into
-    // the padding words of the attribute record
-    std::vector<hiprz_tri> dtris(sc->tris, sc->tris + sc->n_tris);
-    std::vector<hiprz_tri_attr> dattrs(sc->tri_attrs, sc->tri_attrs + sc->n_tris);
-    for (uint32_t i = 0; i < sc->n_tris; ++i) {
-        hiprz_tri& t = dtris[i];
-        hiprz_tri_attr& a = dattrs[i];
-        if (!own_trees || identity_order) t.pad0 = i;  // position in the reference's leaf order: what equally distant hits are ranked by
-        a.pad0 = t.v2[0], a.pad1 = t.v2[1], a.pad2 = t.v2[2], a.pad3 = t.v3[0], a.pad4[0] = t.v3[1], a.pad4[1] = t.v3[2];
-        for (int k = 0; k < 3; ++k) {
-            const float v2 = t.v2[k], v3 = t.v3[k];
-            t.v2[k] = v2 - t.v1[k];
-            t.v3[k] = v3 - t.v1[k];
-        }
-    }
-    d.off_tris = append(dtris.data(), sizeof(hiprz_tri) * dtris.size());
-    d.off_tri_attrs = append(dattrs.data(), sizeof(hiprz_tri_attr) * dattrs.size());
-    d.off_materials = append(sc->materials, sizeof(hiprz_material) * sc->n_materials);
-    d.off_inst_materials = append(sc->inst_materials, sizeof(int32_t) * sc->n_inst_materials);
-    if (blob.size() > 0xFFFFFFF0ull) return fail(c, HIPRZ_ERR_INVALID, "scene geometry exceeds 4 GiB");
-    d.hot_bytes = uint32_t(blob.size());
-
-    // HIPRZ_TREE_DEVICE: the node arrays get room behind the uploaded prefix for the world tree (2 * instances + 1 slots) and for every
-    // mesh tree (2 * triangles - 1 slots) the device is going to build; regions start at odd slots, their child pairs at even ones
-    const bool device_trees = own_trees && tree == HIPRZ_TREE_DEVICE;
-    std::vector<DeviceMesh> device_meshes;
-    std::vector<uint32_t> instance_mesh(sc->n_instances, RZ_END);
-    uint32_t node_capacity = uint32_t(dnodes.size()), world_region = 0u;
-    if (device_trees) {
-        std::vector<uint32_t> mesh_of_root(sc->n_nodes, RZ_END);
-        for (uint32_t i = 0; i < sc->n_instances; ++i) {
-            const uint32_t root = sc->instances[i].blas_root;
-            if (root >= sc->n_nodes) continue;
-            if (mesh_of_root[root] == RZ_END) {
-                const hiprz_node& leaf = sc->nodes[root];  // the placeholder of hiprz_rebuild_mesh_trees(.., HIPRZ_TREE_DEVICE, ..): one leaf per mesh
-                DeviceMesh m;
-                m.tri_first = leaf.begin, m.n_tris = leaf.meta & HIPRZ_NODE_COUNT_MASK;
-                m.ref_first = m.n_tris ? (identity_order ? leaf.begin : sc->tris[leaf.begin].pad0) : 0u;
-                m.leaf_slot = new_index[root];
-                std::memcpy(m.bb_min, leaf.bb_min, 12), std::memcpy(m.bb_max, leaf.bb_max, 12);
-                mesh_of_root[root] = uint32_t(device_meshes.size());
-                device_meshes.push_back(m);
-            }
-            instance_mesh[i] = mesh_of_root[root];
-        }
-        uint32_t cursor = uint32_t(dnodes.size());
-        if (!(cursor & 1u)) cursor += 1u;
-        world_region = cursor;
-        cursor += 2u * sc->n_instances + 1u;
-        node_capacity = device_build_regions(device_meshes, cursor);
-        dskip.resize(node_capacity, RZ_END);
-    }
-    RZ_HIP(c, c->hot.assign(blob.data(), blob.size(), c->stream));
-    RZ_HIP(c, c->node_skip.assign(dskip.data(), dskip.size(), c->stream));
-    if (device_trees) {
-        hiprz_node unused{};
-        unused.meta = HIPRZ_NODE_LEAF;  // slots no build fills stay empty leaves nothing links to
-        std::vector<hiprz_node> all(node_capacity, unused);
-        std::copy(dnodes.begin(), dnodes.end(), all.begin());
-        RZ_HIP(c, c->dev_nodes.assign(reinterpret_cast<const uint8_t*>(all.data()), all.size() * sizeof(hiprz_node), c->stream));
-        RZ_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    // front-to-back walk: 64-B records, node (interleaved box) + the 8 octant links
-    std::vector<uint32_t> nodes64(size_t(node_capacity ? node_capacity : 1) * 16u, RZ_END);
-    for (size_t n = 0; n < dnodes.size(); ++n) {
-        std::memcpy(&nodes64[n * 16u], &dnodes[n], sizeof(hiprz_node));
-        std::memcpy(&nodes64[n * 16u + 8u], &derived.dskip8[n * 8u], 32);
-    }
-    RZ_HIP(c, c->nodes64.assign(nodes64.data(), nodes64.size(), c->stream));
-    RZ_HIP(c, c->textures.assign(sc->textures, sc->n_textures, c->stream));
-    RZ_HIP(c, c->texels.assign(sc->texels, sc->texel_bytes, c->stream));
-    RZ_HIP(c, c->spot_lights.assign(sc->spot_lights, sc->n_spot_lights, c->stream));
-    RZ_HIP(c, c->direct_lights.assign(sc->direct_lights, sc->n_direct_lights, c->stream));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));  // host staging vectors and the caller's arrays may go away after return
-
-    d.hot = reinterpret_cast<const float4*>(c->hot.ptr);
-    d.nodes = reinterpret_cast<const float4*>(c->hot.ptr + d.off_nodes);
-    d.tlas_order = reinterpret_cast<const uint32_t*>(c->hot.ptr + d.off_tlas_order);
-    d.instances = reinterpret_cast<const float4*>(c->hot.ptr + d.off_instances);
-    d.tris = reinterpret_cast<const float4*>(c->hot.ptr + d.off_tris);
-    d.tri_attrs = reinterpret_cast<const float4*>(c->hot.ptr + d.off_tri_attrs);
-    d.materials = reinterpret_cast<const float4*>(c->hot.ptr + d.off_materials);
-    d.inst_materials = reinterpret_cast<const int32_t*>(c->hot.ptr + d.off_inst_materials);
-    d.fast_div = fast_div ? 1u : 0u;
-    d.textures = reinterpret_cast<const float4*>(c->textures.ptr);
-    d.texels = c->texels.ptr;
-    d.spot_lights = reinterpret_cast<const float4*>(c->spot_lights.ptr);
-    d.direct_lights = reinterpret_cast<const float4*>(c->direct_lights.ptr);
-    d.n_instances = sc->n_instances;
-    d.tlas_root = sc->n_instances ? new_index[sc->tlas_root] : 0u;
-    d.node_skip = c->node_skip.ptr;
-    for (int a = 0; a < 3; ++a) {
-        const float lo = sc->n_instances ? sc->nodes[sc->tlas_root].bb_min[a] : 0.0f, hi = sc->n_instances ? sc->nodes[sc->tlas_root].bb_max[a] : 0.0f;
-        d.bounds_min[a] = lo;
-        d.bounds_scale[a] = hi > lo ? 32.0f / (hi - lo) : 0.0f;
-    }
-    d.top_count = std::min<uint32_t>(uint32_t(dnodes.size()), kTopCacheNodes);
-    d.nodes64 = reinterpret_cast<const float4*>(c->nodes64.ptr);
-    c->n_nodes = sc->n_nodes;
-    c->flat_world = sc->n_instances != 0u && (sc->nodes[sc->tlas_root].meta & HIPRZ_NODE_LEAF) && (sc->nodes[sc->tlas_root].meta & HIPRZ_NODE_COUNT_MASK) <= 8u;
-    c->n_textures = sc->n_textures;
-    // mesh walk rounds of at most 4 node steps and 8 triangles per lane (measured: D 3 163 -> 2 891 us, C 935 -> 892 us)
-    d.walk_k = 4u, d.walk_l = 8u;
-    d.walk_h = 65u;  // never: ending the node phase early for a full triangle step measured no gain (D 1 010 vs 999 us)
-    // ray reordering key: where only the closest-hit walk follows the sorted order, the origin's cell interleaved with where the ray is
-    // going groups best (config C, the 6-D Morton code of cell and direction: trace kernel 583 -> 503 us; round 4: the direction on the
-    // octahedron, E 2 682 -> 2 556 us, C 324 -> 316; then the cell where the ray leaves the world box instead of a direction, E -> 2 400,
-    // C -> 299); where the deferred shadow rays follow that order too (HIPRZ_SHADOW_SORT=0) they fan out from the origin cell, so the
-    // origin leads (config E: 86.5 ms per step against 92.6)
-    d.sort_variant = (sc->n_spot_lights + sc->n_direct_lights) && c->shadow_sort == 0 ? 0u : 4u;
-    // the shadow rays' key: the pixel's set of sample slots (+ 0x100: the shadow kernel's loop over the slots is wave-uniform, a slot few of a
-    // wave's pixels hold costs the wave a whole walk; E 40.33 -> 39.85 ms), then the light the ray goes to and the origin's cell in a 64^3
-    // grid (+ 0x400; E 38.5 -> 37.8 ms against layout 0 — cell, then direction —, which was the best of the layouts: the rays fan out from the cell)
-    d.shadow_variant = 0x500u;
-    if (const char* v = std::getenv("HIPRZ_SHADOW_KEY")) d.shadow_variant = uint32_t(std::atoi(v));
-    if (const char* v = std::getenv("HIPRZ_SORT_KEY")) d.sort_variant = uint32_t(std::atoi(v));
-    // The world and instance levels of the cooperative walks ("while-while" one and two levels above the mesh walk; the order in which a
-    // lane meets its instances stays the reference's).  World level: a lane steps through up to 1 + 8 nodes of the world tree per round
-    // until it HOLDS a leaf with instances, so that the expensive part — the ray into an instance's space, the mesh walk — runs for many
-    // lanes at once instead of for the few that happened to reach a leaf in this step (E, 46 instances: trace kernel 3 010 -> 2 678 us,
-    // shade + shadow 2 711 -> 2 636; 1 / 2 / 4 / 8 / 64 further steps: 2 992 / 2 892 / 2 798 / 2 712 / 2 716 us).  Instance level: a lane
-    // that misses an instance's box tests the next one in the same round (D 836 -> 803 us; with 4 and more D's lanes reach the big mesh
-    // in different rounds, each as long as its longest walk: 1 045 us and worse).  profiles/r03/ab_instance_advance.txt, ab_world_advance.txt
-    d.walk_advance = 1u;
-    d.world_advance = 8u;
-    if (const char* v = std::getenv("HIPRZ_WALK_ADVANCE")) d.walk_advance = uint32_t(std::atoi(v));
-    if (const char* v = std::getenv("HIPRZ_WORLD_ADVANCE")) d.world_advance = uint32_t(std::atoi(v));
-    if (const char* v = std::getenv("HIPRZ_WALK_K")) d.walk_k = uint32_t(std::atoi(v));
-    if (const char* v = std::getenv("HIPRZ_WALK_L")) d.walk_l = uint32_t(std::atoi(v));
-    if (const char* v = std::getenv("HIPRZ_WALK_H")) d.walk_h = uint32_t(std::atoi(v));
-    d.n_spot_lights = sc->n_spot_lights;
-    d.n_direct_lights = sc->n_direct_lights;
-    // Stage the blob in LDS when three workgroups per CU (the kernel's register-limited residency)
-    // still fit into the CU's 160 KiB together with their traversal stacks.
-    c->lds_scene = size_t(d.hot_bytes) + size_t(c->stack_entries) * 1024u + BinnedLds::kFixedBytes <= kLdsSceneLimit;
-    c->scene_tree = own_trees ? tree : HIPRZ_TREE_REFERENCE;
-    if (own_trees) c->lds_scene = false;  // rebuilt trees are walked front to back on skip links only (ties by reference position)
-    c->n_tris = sc->n_tris, c->n_tlas_order = sc->n_tlas_order;
-    c->device_meshes.clear(), c->instance_mesh.clear();
-    if (device_trees) {
-        const bool validate = !std::getenv("HIPRZ_TRUST_DEVICE_TREES");
-        d.nodes = reinterpret_cast<const float4*>(c->dev_nodes.ptr);
-        c->node_capacity = node_capacity, c->world_region = world_region;
-        c->device_instances = dinstances;
-        std::vector<uint8_t> has_mesh(sc->n_instances ? sc->n_instances : 1u, 0);
-        for (uint32_t i = 0; i < sc->n_instances; ++i) has_mesh[i] = instance_mesh[i] != RZ_END ? 1 : 0;
-        RZ_HIP(c, c->has_mesh.assign(has_mesh.data(), has_mesh.size(), c->stream));
-        RZ_HIP(c, hipStreamSynchronize(c->stream));
-        RZ_HIP(c, c->slot_parent.resize(node_capacity));
-        RZ_HIP(c, hipMemsetAsync(c->slot_parent.ptr, 0xFF, size_t(node_capacity) * sizeof(uint32_t), c->stream));  // RZ_END: the single leaves of small meshes have no parent
-        int rc = HIPRZ_OK;
-        if (sc->n_tlas_order) {
-            rc = device_build_world_tree(c, validate);
-            if (rc != HIPRZ_OK) return rc;
-            d.tlas_root = world_region;
-        }
-        rc = device_build_mesh_trees(c, device_meshes, instance_mesh, validate);
-        if (rc != HIPRZ_OK) return rc;
-        c->instance_mesh = instance_mesh;
-        for (uint32_t i = 0; i < sc->n_instances; ++i)
-            if (instance_mesh[i] != RZ_END && c->device_meshes[instance_mesh[i]].region != RZ_END) c->device_instances[i].blas_root = c->device_meshes[instance_mesh[i]].region;
-        uint32_t emitted = c->world_slots;
-        for (const auto& m : c->device_meshes) emitted += m.n_slots;
-        c->n_nodes = emitted;
-    }
-    {   // the shadow rays' own world tree over the instances of the world tree (those with a mesh)
-        std::vector<uint8_t> member(sc->n_instances ? sc->n_instances : 1u, 0);
-        for (uint32_t k = 0; k < sc->n_tlas_order; ++k)
-            if (sc->tlas_order[k] < sc->n_instances) member[sc->tlas_order[k]] = 1;
-        c->world_members.clear();
-        for (uint32_t i = 0; i < sc->n_instances; ++i)
-            if (member[i]) c->world_members.push_back(i);
-        const int src = build_shadow_world_tree(c, dinstances, d);
-        if (src != HIPRZ_OK) return src;
-    }
-    c->have_scene = true;
-    resolve_pipeline(c);
-    c->reset_pending = true;  // world changed => accumulation restarts (cpu_engine_renderer.cpp:108-112), for every camera
-    stale_guides(c);
-    for (auto& f : c->parked) f.reset_pending = true;
-    c->timings.set("upload scene", timer.ms());
-    return HIPRZ_OK;
-}
-
-// Materials and lights of the uploaded scene changed, geometry did not (the reference's dirty flags per container, updatable.cpp:23-51;
-// Cuda::World re-mirrors only modified containers, cuda_world.cu:28-57): the records are replaced in place — no tree is rebuilt,
-// re-derived or re-validated.  The material count must be that of the uploaded scene (instances refer to materials by index).
-int hiprz_update_shading(hiprz_ctx* c, const hiprz_material* materials, uint32_t n_materials, const hiprz_spot_light* spot_lights,
-                         uint32_t n_spot_lights, const hiprz_direct_light* direct_lights, uint32_t n_direct_lights) {
-    if (!c) return HIPRZ_ERR_INVALID;
-    RZ_FANOUT_OTHER_DEVICES(c, hiprz_update_shading(p, materials, n_materials, spot_lights, n_spot_lights, direct_lights, n_direct_lights));
-    struct Share {
-        hiprz_ctx* c;
-        ~Share() { share_scene_with_streams(c); }
-    } share{c};
-    for (hiprz_ctx* p : c->peers)  // streams on this device read the records that are about to be replaced
-        if (p->device == c->device) (void)hipStreamSynchronize(p->stream);
-    if (!c->have_scene) return fail(c, HIPRZ_ERR_STATE, "update_shading before upload_scene");
-    const uint32_t uploaded = (c->dscene.off_inst_materials - c->dscene.off_materials) / uint32_t(sizeof(hiprz_material));
-    if (!materials || n_materials < 2u || ((n_materials * sizeof(hiprz_material) + 15u) & ~size_t(15)) != size_t(c->dscene.off_inst_materials - c->dscene.off_materials))
-        return fail(c, HIPRZ_ERR_INVALID, "update_shading: the scene was uploaded with " + std::to_string(uploaded) + " material slots");
-    if ((n_spot_lights && !spot_lights) || (n_direct_lights && !direct_lights)) return fail(c, HIPRZ_ERR_INVALID, "update_shading: null array with non-zero count");
-    std::vector<hiprz_texture> tex(c->n_textures);
-    (void)hipSetDevice(c->device);
-    if (c->n_textures) RZ_HIP(c, hipMemcpy(tex.data(), c->textures.ptr, sizeof(hiprz_texture) * c->n_textures, hipMemcpyDeviceToHost));
-    auto tex_ok = [&](int32_t t, uint32_t kind) { return t < 0 || (uint32_t(t) < c->n_textures && tex[t].kind == kind); };
-    for (uint32_t i = 0; i < n_materials; ++i) {
-        const hiprz_material& m = materials[i];
-        if (!tex_ok(m.texture, HIPRZ_TEX_RGBA8) || !tex_ok(m.normal_map, HIPRZ_TEX_RGBA8) || !tex_ok(m.metalness_map, HIPRZ_TEX_R8) ||
-            !tex_ok(m.roughness_map, HIPRZ_TEX_R8) || !tex_ok(m.emission_map, HIPRZ_TEX_R32F))
-            return fail(c, HIPRZ_ERR_INVALID, "update_shading: material " + std::to_string(i) + ": map index/kind invalid");
-    }
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    RZ_HIP(c, hipMemcpy(c->hot.ptr + c->dscene.off_materials, materials, sizeof(hiprz_material) * n_materials, hipMemcpyHostToDevice));
-    RZ_HIP(c, c->spot_lights.assign(spot_lights, n_spot_lights, c->stream));
-    RZ_HIP(c, c->direct_lights.assign(direct_lights, n_direct_lights, c->stream));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    c->dscene.spot_lights = reinterpret_cast<const float4*>(c->spot_lights.ptr);
-    c->dscene.direct_lights = reinterpret_cast<const float4*>(c->direct_lights.ptr);
-    c->dscene.n_spot_lights = n_spot_lights, c->dscene.n_direct_lights = n_direct_lights;
-    const bool no_shadow_sort = (n_spot_lights + n_direct_lights) && c->shadow_sort == 0;
-    if (!std::getenv("HIPRZ_SORT_KEY")) c->dscene.sort_variant = no_shadow_sort ? 0u : 4u;
-    invalidate_graphs(c);
-    c->reset_pending = true;  // the world changed: accumulation restarts (cpu_engine_renderer.cpp:108-112), for every camera
-    stale_guides(c);
-    for (auto& f : c->parked) f.reset_pending = true;
-    return HIPRZ_OK;
-}
-
-// ---- geometry changes without a host-side tree build (scenes uploaded under HIPRZ_TREE_DEVICE; hiprz_build.hip) ----
-namespace {
-// An in-place change of the scene failed half way (a device-built tree the host refused to prove terminating, a device error): the node
-// tables, the triangle order or the instance roots may be part old, part new — there is no scene any more.  hiprz_render then returns
-// HIPRZ_ERR_STATE instead of walking tables nobody proved, and the streams that share this device's copy learn the same (Share's destructor).
-int scene_lost(hiprz_ctx* c, int rc) {
-    c->have_scene = false;
-    c->device_meshes.clear(), c->instance_mesh.clear();
-    invalidate_graphs(c);
-    return rc;
-}
-// The shadow rays' own world tree.  anyIntersection's answer does not depend on the order in which a ray meets the instances, so the
-// wave-level shadow walk (any_hit_packet) need not follow the reference's world tree — built for another purpose: leaves of several
-// instances, met in one fixed sequence — and takes a binned-free surface-area tree over the instances' world boxes instead: binary, one
-// instance per leaf, the leaf's box being the instance's own (interleaved) box bit for bit, so that the leaf's test is the instance's
-// test.  Built on the host from the instance records the device holds (`dinst`: boxes interleaved like nodes), at every upload and every
-// hiprz_update_instances: n log^2 n for n instances, 64-byte walk records with the octant-0 skip links the wave-level walk follows,
-// root in record 0.  Buffers are sized once per scene (2 n records), so the DScene a captured graph holds stays valid across updates.
-int build_shadow_world_tree(hiprz_ctx* c, const std::vector<hiprz_instance>& dinst, DScene& d) {
-    d.shadow_nodes64 = nullptr, d.shadow_order = nullptr, d.shadow_root = RZ_END;
-    const std::vector<uint32_t>& members = c->world_members;
-    // Where it pays (the living room's pass, wave-level walk on this tree / on the reference's / cooperative walk, ms): 40 instances at 4K 4.20 / 4.34 /
-    // 4.75, 100 at 4K 5.91 / 6.13 / 6.65, 100 at 1080p 2.09 / 2.17 / 2.28, 300 at 4K 9.00 / 8.84 / 9.29 — a deep binary tree is a long chain of
-    // dependent steps for a wave that crosses many instances; beyond 160 the walk keeps the reference's tree (and the host is spared the build).
-    if (!c->shadow_tree || members.empty() || members.size() > 160u) return HIPRZ_OK;
-    struct Box {
-        float mn[3], mx[3];
-    };
-    auto box_of = [&](uint32_t i) {
-        const hiprz_instance& in = dinst[i];
-        float max_y;
-        std::memcpy(&max_y, &in.pad2, 4);
-        return Box{{in.bb_min[0], in.bb_min[2], in.bb_max[0]}, {in.bb_min[1], max_y, in.bb_max[1]}};
-    };
-    auto grow = [](Box& b, const Box& o) {
-        for (int a = 0; a < 3; ++a) b.mn[a] = std::min(b.mn[a], o.mn[a]), b.mx[a] = std::max(b.mx[a], o.mx[a]);
-    };
-    auto area = [](const Box& b) {
-        const float x = b.mx[0] - b.mn[0], y = b.mx[1] - b.mn[1], z = b.mx[2] - b.mn[2];
-        return x * y + y * z + z * x;
-    };
-    const uint32_t n = uint32_t(members.size());
-    std::vector<uint32_t> order(members), rec(size_t(2u * n) * 16u, RZ_END), sorted, best;
-    std::vector<float> left_area;
-    struct Task {
-        uint32_t node, lo, hi, link;
-    };
-    std::vector<Task> stack{{0u, 0u, n, RZ_END}};
-    uint32_t next_free = 1u;
-    while (!stack.empty()) {
-        const Task t = stack.back();
-        stack.pop_back();
-        Box b = box_of(order[t.lo]);
-        for (uint32_t k = t.lo + 1u; k < t.hi; ++k) grow(b, box_of(order[k]));
-        const float interleaved[6] = {b.mn[0], b.mx[0], b.mn[1], b.mx[1], b.mn[2], b.mx[2]};
-        uint32_t* r = &rec[size_t(t.node) * 16u];
-        std::memcpy(r, interleaved, 24);
-        for (int o = 0; o < 8; ++o) r[8 + o] = t.link;  // (only the wave-level walk follows this tree: the order of octant 0 under every octant)
-        const uint32_t len = t.hi - t.lo;
-        if (len == 1u) {
-            r[6] = t.lo, r[7] = HIPRZ_NODE_LEAF | 1u;
-            continue;
-        }
-        // the cheapest cut of the instances sorted by box centre along one of the axes: area(left) * |left| + area(right) * |right|
-        float best_cost = 3.0e38f;
-        uint32_t best_axis = 0u, best_cut = len / 2u;
-        for (uint32_t axis = 0; axis < 3u; ++axis) {
-            sorted.assign(order.begin() + t.lo, order.begin() + t.hi);
-            std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t x, uint32_t y) {
-                const Box bx = box_of(x), by = box_of(y);
-                return bx.mn[axis] + bx.mx[axis] < by.mn[axis] + by.mx[axis];
-            });
-            left_area.assign(len, 0.0f);
-            Box acc = box_of(sorted[0]);
-            for (uint32_t k = 1u; k < len; ++k) left_area[k] = area(acc), grow(acc, box_of(sorted[k]));  // area of the first k
-            acc = box_of(sorted[len - 1u]);
-            for (uint32_t k = len - 1u; k >= 1u; --k) {  // cut before position k
-                const float cost = left_area[k] * float(k) + area(acc) * float(len - k);
-                if (cost < best_cost) best_cost = cost, best_axis = axis, best_cut = k, best = sorted;
-                grow(acc, box_of(sorted[k - 1u]));
-            }
-        }
-        if (best.size() != len) best.assign(order.begin() + t.lo, order.begin() + t.hi);
-        std::copy(best.begin(), best.end(), order.begin() + t.lo);
-        best.clear();
-        const uint32_t first = next_free;
-        next_free += 2u;
-        r[6] = first, r[7] = (2u - best_axis) << HIPRZ_NODE_PTYPE_SHIFT;  // the lower child along the axis first
-        stack.push_back({first + 1u, t.lo + best_cut, t.hi, t.link});
-        stack.push_back({first, t.lo, t.lo + best_cut, first + 1u});
-    }
-    (void)hipSetDevice(c->device);
-    RZ_HIP(c, c->shadow_nodes64.resize(rec.size()));
-    RZ_HIP(c, c->shadow_order.resize(n));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    RZ_HIP(c, hipMemcpy(c->shadow_nodes64.ptr, rec.data(), rec.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    RZ_HIP(c, hipMemcpy(c->shadow_order.ptr, order.data(), size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    d.shadow_nodes64 = reinterpret_cast<const float4*>(c->shadow_nodes64.ptr), d.shadow_order = c->shadow_order.ptr, d.shadow_root = 0u;
-    return HIPRZ_OK;
-}
-
-int restart_after_geometry_change(hiprz_ctx* c) {
-    c->reset_pending = true;  // the world changed: accumulation restarts (cpu_engine_renderer.cpp:108-112), for every camera
-    stale_guides(c);
-    for (auto& f : c->parked) f.reset_pending = true;
-    return HIPRZ_OK;
-}
-}  // namespace
-
-int hiprz_update_triangles(hiprz_ctx* c, uint32_t first, uint32_t n, const hiprz_tri* tris, const hiprz_tri_attr* attrs) {
-    if (!c) return HIPRZ_ERR_INVALID;
-    RZ_FANOUT_OTHER_DEVICES(c, hiprz_update_triangles(p, first, n, tris, attrs));
-    struct Share {
-        hiprz_ctx* c;
-        ~Share() { share_scene_with_streams(c); }
-    } share{c};
-    for (hiprz_ctx* p : c->peers)
-        if (p->device == c->device) (void)hipStreamSynchronize(p->stream);
-    if (!c->have_scene || c->scene_tree != HIPRZ_TREE_DEVICE) return fail(c, HIPRZ_ERR_STATE, "update_triangles: the scene was not uploaded under HIPRZ_TREE_DEVICE");
-    if (n == 0u) return HIPRZ_OK;
-    if (!tris || !attrs || uint64_t(first) + n > c->n_tris) return fail(c, HIPRZ_ERR_INVALID, "update_triangles: range outside the uploaded triangles");
-    for (uint32_t k = 0; k < n; ++k)  // the walks divide by nothing here, but the shading indexes material slots
-        if ((tris[k].material_flags & HIPRZ_TRI_MATERIAL_MASK) > 0xFFFFFFu) return fail(c, HIPRZ_ERR_INVALID, "update_triangles: bad material id");
-    (void)hipSetDevice(c->device);
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    const int rc = device_update_triangles(c, first, n, tris, attrs);
-    if (rc != HIPRZ_OK) return scene_lost(c, rc);
-    return restart_after_geometry_change(c);
-}
-
-int hiprz_rebuild_trees(hiprz_ctx* c, uint32_t tree) {
-    if (!c) return HIPRZ_ERR_INVALID;
-    RZ_FANOUT_OTHER_DEVICES(c, hiprz_rebuild_trees(p, tree));
-    struct Share {
-        hiprz_ctx* c;
-        ~Share() { share_scene_with_streams(c); }
-    } share{c};
-    for (hiprz_ctx* p : c->peers)
-        if (p->device == c->device) (void)hipStreamSynchronize(p->stream);
-    if (!c->have_scene || c->scene_tree != HIPRZ_TREE_DEVICE) return fail(c, HIPRZ_ERR_STATE, "rebuild_trees: the scene's trees were not built on the device");
-    if (tree != HIPRZ_TREE_DEVICE && tree != HIPRZ_TREE_DEVICE_SAH) return fail(c, HIPRZ_ERR_INVALID, "rebuild_trees: HIPRZ_TREE_DEVICE or HIPRZ_TREE_DEVICE_SAH");
-    (void)hipSetDevice(c->device);
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    invalidate_graphs(c);
-    c->build_sah = tree == HIPRZ_TREE_DEVICE_SAH;
-    // the meshes' bounds as they are now: the box of every root (exact after a refit)
-    std::vector<DeviceMesh> meshes = c->device_meshes;
-    for (DeviceMesh& m : meshes) {
-        const uint32_t root = m.region != RZ_END ? m.region : m.leaf_slot;
-        if (root == RZ_END || m.n_tris == 0u) continue;
-        float rec[8];
-        RZ_HIP(c, hipMemcpy(rec, c->dev_nodes.ptr + size_t(root) * sizeof(hiprz_node), sizeof rec, hipMemcpyDeviceToHost));
-        m.bb_min[0] = rec[0], m.bb_max[0] = rec[1], m.bb_min[1] = rec[2], m.bb_max[1] = rec[3], m.bb_min[2] = rec[4], m.bb_max[2] = rec[5];
-    }
-    const std::vector<uint32_t> instance_mesh = c->instance_mesh;
-    const int rc = device_build_mesh_trees(c, meshes, instance_mesh, !std::getenv("HIPRZ_TRUST_DEVICE_TREES"));
-    if (rc != HIPRZ_OK) return scene_lost(c, rc);  // nodes, links and the triangle order were being rewritten in place
-    for (size_t i = 0; i < c->device_instances.size(); ++i)
-        if (c->instance_mesh[i] != RZ_END && c->device_meshes[c->instance_mesh[i]].region != RZ_END)
-            c->device_instances[i].blas_root = c->device_meshes[c->instance_mesh[i]].region;
-    uint32_t emitted = c->world_slots;
-    for (const auto& m : c->device_meshes) emitted += m.n_slots;
-    c->n_nodes = emitted;
-    resolve_pipeline(c);
-    return restart_after_geometry_change(c);
-}
-
-int hiprz_update_instances(hiprz_ctx* c, const hiprz_instance* instances, uint32_t n) {
-    if (!c) return HIPRZ_ERR_INVALID;
-    RZ_FANOUT_OTHER_DEVICES(c, hiprz_update_instances(p, instances, n));
-    struct Share {
-        hiprz_ctx* c;
-        ~Share() { share_scene_with_streams(c); }
-    } share{c};
-    for (hiprz_ctx* p : c->peers)
-        if (p->device == c->device) (void)hipStreamSynchronize(p->stream);
-    if (!c->have_scene || c->scene_tree != HIPRZ_TREE_DEVICE) return fail(c, HIPRZ_ERR_STATE, "update_instances: the scene was not uploaded under HIPRZ_TREE_DEVICE");
-    if (!instances || n != c->dscene.n_instances || n != c->device_instances.size()) return fail(c, HIPRZ_ERR_INVALID, "update_instances: the scene was uploaded with " + std::to_string(c->dscene.n_instances) + " instances");
-    bool fast_div = c->dscene.fast_div != 0u;
-    auto coord_ok = [](float x) {
-        uint32_t b;
-        std::memcpy(&b, &x, 4);
-        const uint32_t e = (b >> 23) & 0xFFu;
-        return (b & 0x7FFFFFFFu) == 0u || (e >= 127u - 60u && e < 127u + 40u);
-    };
-    for (uint32_t i = 0; i < n; ++i) {
-        hiprz_instance& d = c->device_instances[i];  // keeps blas_root (the device-built root), the material table and the padding flags
-        const hiprz_instance& in = instances[i];
-        std::memcpy(d.position, in.position, 12), std::memcpy(d.scale, in.scale, 12);
-        std::memcpy(d.x_axis, in.x_axis, 12), std::memcpy(d.y_axis, in.y_axis, 12), std::memcpy(d.z_axis, in.z_axis, 12);
-        d.pad0 = (in.scale[0] == 1.0f && in.scale[1] == 1.0f && in.scale[2] == 1.0f) ? 1u : 0u;
-        const float v[6] = {in.bb_min[0], in.bb_max[0], in.bb_min[1], in.bb_max[1], in.bb_min[2], in.bb_max[2]};  // interleaved like nodes
-        d.bb_min[0] = v[0], d.bb_min[1] = v[1], d.bb_min[2] = v[2];
-        std::memcpy(&d.pad2, &v[3], 4);
-        d.bb_max[0] = v[4], d.bb_max[1] = v[5], d.bb_max[2] = 0.0f;
-        for (float x : v) fast_div = fast_div && coord_ok(x);
-    }
-    (void)hipSetDevice(c->device);
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    RZ_HIP(c, hipMemcpy(c->hot.ptr + c->dscene.off_instances, c->device_instances.data(), sizeof(hiprz_instance) * n, hipMemcpyHostToDevice));
-    if (!fast_div && c->dscene.fast_div) c->dscene.fast_div = 0u, invalidate_graphs(c);
-    if (c->n_tlas_order) {
-        const int rc = device_build_world_tree(c, !std::getenv("HIPRZ_TRUST_DEVICE_TREES"));
-        if (rc != HIPRZ_OK) return scene_lost(c, rc);  // the new instance records and a world tree nobody proved are on the device
-    }
-    {
-        const int src = build_shadow_world_tree(c, c->device_instances, c->dscene);  // the instances moved: the shadow rays' tree over them again
-        if (src != HIPRZ_OK) return scene_lost(c, src);
-    }
-    return restart_after_geometry_change(c);
-}
-
-int hiprz_download_trees(hiprz_ctx* c, hiprz_node* nodes_out, uint32_t max_nodes, uint32_t* n_nodes_out, uint32_t* tlas_root_out, uint32_t* tlas_order_out,
-                         uint32_t* blas_roots_out, uint32_t* tri_refpos_out) {
-    if (!c) return HIPRZ_ERR_INVALID;
-    if (!c->have_scene) return fail(c, HIPRZ_ERR_STATE, "download_trees before upload_scene");
-    (void)hipSetDevice(c->device);
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    const bool device_trees = c->scene_tree == HIPRZ_TREE_DEVICE;
-    const uint32_t n_nodes = device_trees ? c->node_capacity : uint32_t((c->dscene.off_tlas_order - c->dscene.off_nodes) / sizeof(hiprz_node));
-    if (n_nodes_out) *n_nodes_out = n_nodes;
-    if (tlas_root_out) *tlas_root_out = c->dscene.tlas_root;
-    if (nodes_out) {
-        if (max_nodes < n_nodes) return fail(c, HIPRZ_ERR_INVALID, "download_trees: " + std::to_string(n_nodes) + " nodes");
-        RZ_HIP(c, hipMemcpy(nodes_out, c->dscene.nodes, sizeof(hiprz_node) * n_nodes, hipMemcpyDeviceToHost));
-        for (uint32_t k = 0; k < n_nodes; ++k) {  // the device keeps boxes interleaved: (min.x, max.x, min.y, max.y, min.z, max.z)
-            hiprz_node& nd = nodes_out[k];
-            const float v[6] = {nd.bb_min[0], nd.bb_min[1], nd.bb_min[2], nd.bb_max[0], nd.bb_max[1], nd.bb_max[2]};
-            nd.bb_min[0] = v[0], nd.bb_max[0] = v[1], nd.bb_min[1] = v[2], nd.bb_max[1] = v[3], nd.bb_min[2] = v[4], nd.bb_max[2] = v[5];
-        }
-    }
-    if (tlas_order_out && c->n_tlas_order) RZ_HIP(c, hipMemcpy(tlas_order_out, c->hot.ptr + c->dscene.off_tlas_order, 4u * c->n_tlas_order, hipMemcpyDeviceToHost));
-    if (blas_roots_out && c->dscene.n_instances) {
-        std::vector<hiprz_instance> inst(c->dscene.n_instances);
-        RZ_HIP(c, hipMemcpy(inst.data(), c->hot.ptr + c->dscene.off_instances, sizeof(hiprz_instance) * inst.size(), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < inst.size(); ++i) blas_roots_out[i] = inst[i].blas_root;
-    }
-    if (tri_refpos_out && c->n_tris) {
-        std::vector<hiprz_tri> tris(c->n_tris);
-        RZ_HIP(c, hipMemcpy(tris.data(), c->hot.ptr + c->dscene.off_tris, sizeof(hiprz_tri) * tris.size(), hipMemcpyDeviceToHost));
-        for (size_t t = 0; t < tris.size(); ++t) tri_refpos_out[t] = tris[t].pad0;
-    }
-    return HIPRZ_OK;
-}
 
 int hiprz_upload_camera(hiprz_ctx* c, const hiprz_camera* cam) {
     if (!c) return HIPRZ_ERR_INVALID;

@@ -23,7 +23,6 @@
 namespace hiprz {
 namespace {
 
-constexpr uint32_t kLeafMax = 4u;  // one quad entry of the cooperative triangle phase
 constexpr uint32_t kLeafBit = 0x80000000u;
 
 struct BuildViews {  // device pointers of one mesh's build (all sized for the mesh's n triangles)
@@ -230,7 +229,7 @@ __global__ void __launch_bounds__(256) rz_build_emit_kernel(BuildViews b, EmitVi
 }
 
 // The skip link of every emitted node under every ray octant, found by climbing: the child a ray of octant o visits first links to
-// its sibling, the other one inherits its parent's link (hiprz_api.hip: derive_tables does the same sweep top-down on the host).
+// its sibling, the other one inherits its parent's link (hiprz_scene_host.cpp: derive_tables does the same sweep top-down on the host).
 // Writes the 64-byte walk records (node + 8 links) and the octant-0 links of the reference-order walks.
 __global__ void __launch_bounds__(256) rz_build_links_kernel(EmitViews e, const uint32_t* n_pairs, uint32_t* nodes64, uint32_t* node_skip) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x, local = idx >> 3, o = idx & 7u;
@@ -1003,24 +1002,8 @@ int build_mesh_sah(hiprz_ctx* c, DeviceMesh& m, float4* blob_tris, float4* blob_
 
 }  // namespace
 
-// Capacity of the node arrays of a scene whose mesh trees are built on the device: the uploaded prefix + per mesh a region of 2n - 1
-// slots starting at an odd index (its child pairs then start at even indices: one 128-byte line per pair of 64-byte walk records).
-uint32_t device_build_regions(std::vector<DeviceMesh>& meshes, uint32_t prefix_nodes) {
-    uint32_t cursor = prefix_nodes;
-    for (auto& m : meshes) {
-        if (m.n_tris <= kLeafMax) {
-            m.region = RZ_END;  // stays the single leaf of the uploaded placeholder
-            continue;
-        }
-        if (!(cursor & 1u)) cursor += 1u;
-        m.region = cursor;
-        cursor += 2u * m.n_tris - 1u;
-    }
-    return cursor;
-}
-
 // Builds the trees of `meshes` on the device into the scene's node arrays (c->dev_nodes, c->node_skip, c->nodes64, sized by the caller
-// through device_build_regions), reorders the triangles of the hot blob accordingly and re-points the instances.  Synchronous.
+// through device_build_regions, hiprz_scene_host.cpp), reorders the triangles of the hot blob accordingly and re-points the instances.  Synchronous.
 int device_build_mesh_trees(hiprz_ctx* c, std::vector<DeviceMesh>& meshes, const std::vector<uint32_t>& instance_mesh, bool validate) {
     StageTimer timer;
     hipStream_t st = c->stream;

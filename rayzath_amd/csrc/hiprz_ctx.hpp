@@ -1,7 +1,8 @@
 // hiprz_ctx.hpp — host-side state of a context (struct hiprz_ctx) and what the translation units of libhiprz.so share:
-// hiprz_api.hip (context life cycle, scene upload and updates, settings, the render loop), hiprz_readback.hip (parts -> frame: tone map,
-// assembly, reads, tile export, present), hiprz_launch_*.hip (the pass kernels' instantiations and their launch logic), hiprz_sort.hip
-// (ray reordering), hiprz_build.hip (trees built on the device) and hiprz_denoise.hip (denoising).
+// hiprz_api.hip (context life cycle, settings, the render loop), hiprz_scene.hip (scene upload and updates; its pure-host half is
+// hiprz_scene_host.cpp), hiprz_readback.hip (parts -> frame: tone map, assembly, reads, tile export, present), hiprz_launch_*.hip (the
+// pass kernels' instantiations and their launch logic), hiprz_sort.hip (ray reordering), hiprz_build.hip (trees built on the device)
+// and hiprz_denoise.hip (denoising).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 
 #include "hiprz.h"
 #include "hiprz_device.hpp"
+#include "hiprz_scene_host.hpp"  // DeviceMesh
 
 namespace hiprz {
 
@@ -101,18 +103,6 @@ struct PartCopy {  // one copy of a push
     size_t bytes;
 };
 
-}  // namespace hiprz
-
-namespace hiprz {
-// one mesh of a scene whose trees are built on the device (hiprz_build.hip)
-struct DeviceMesh {
-    uint32_t tri_first = 0, n_tris = 0;  // its triangles in the device order
-    uint32_t ref_first = 0;              // ... and in the uploaded snapshot's order (a mesh's triangles are contiguous in both)
-    uint32_t region = 0xFFFFFFFFu;       // slot of its root in the node arrays (RZ_END: too small to build, stays one leaf)
-    uint32_t leaf_slot = 0xFFFFFFFFu;    // ... the slot of that one leaf (the uploaded placeholder), whose box a refit fits again
-    uint32_t n_slots = 0;                // nodes emitted
-    float bb_min[3] = {0, 0, 0}, bb_max[3] = {0, 0, 0};
-};
 }  // namespace hiprz
 
 // What belongs to ONE camera of the world: its record, the per-pixel path state and accumulators, the device-resident pass index, the
@@ -410,6 +400,8 @@ constexpr uint32_t kTopCacheNodes = 682u;        // 682 x 36 B = 24 KiB per work
 constexpr size_t kLdsSceneLimit = 52u * 1024u;   // per workgroup: 3 x 52 KiB < 160 KiB per CU
 
 // choices derived from the context's settings and the uploaded scene (hiprz_api.hip)
+void invalidate_graphs(hiprz_ctx* c);  // of every camera: settings and the scene are shared by the cameras of a context
+void resolve_pipeline(hiprz_ctx* c);   // reads the uploaded scene's fields: whoever changes them calls it
 int effective_mode(const hiprz_ctx* c);
 bool defer_shadows(const hiprz_ctx* c);
 bool use_lds_scene(const hiprz_ctx* c);
@@ -451,7 +443,6 @@ void join_sort(hiprz_ctx* c);
 void launch_shadow_sort(hiprz_ctx* c);  // keys of the pass's shadow rays -> the order the shadow kernel follows
 void launch_sort_identity(hiprz_ctx* c);  // the identity order (no sort has run on this frame's rays yet)
 // device-side tree build and refit (hiprz_build.hip)
-uint32_t device_build_regions(std::vector<DeviceMesh>& meshes, uint32_t first_free_slot);
 int device_build_mesh_trees(hiprz_ctx* c, std::vector<DeviceMesh>& meshes, const std::vector<uint32_t>& instance_mesh, bool validate);
 int device_build_world_tree(hiprz_ctx* c, bool validate);
 int device_update_triangles(hiprz_ctx* c, uint32_t first, uint32_t n, const hiprz_tri* tris, const hiprz_tri_attr* attrs);

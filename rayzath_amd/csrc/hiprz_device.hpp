@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "hiprz.h"
+#include "hiprz_end.hpp"
 #include "hiprz_shard.hpp"
 
 namespace hiprz {
@@ -34,8 +35,7 @@ namespace hiprz {
 #define RZ_TRACE_MIN_WAVES 5
 #endif
 #define RZ_PI_F 3.14159265358979323846f
-#define RZ_END 0xFFFFFFFFu
-// Termination of every walk is proven on the host before anything is launched (hiprz_api.hip: check_scene walks the
+// Termination of every walk is proven on the host before anything is launched (hiprz_scene_host.cpp: check_scene walks the
 // uploaded trees, derive_tables walks the derived links), so the loops need no step budget.  -DRZ_WALK_GUARD=1 adds
 // one anyway (debug builds: a wrong table then gives wrong pixels instead of a hung wave); it costs 9 % on config B.
 #define RZ_GUARD_LIMIT (1u << 26)
@@ -104,7 +104,7 @@ struct DScene {
     // ray-direction octants
     const float4* nodes64;
     uint32_t shadow_variant;  // the same for the shadow rays' key (HIPRZ_SHADOW_KEY); + 0x100: the pixel's set of sample slots leads the key; + 0x400: the light the ray goes to, then the origin's cell in a 64^3 grid, instead of a layout
-    // the shadow rays' own world tree (hiprz_api.hip: build_shadow_world_tree): 64-byte walk records, the instance ids its leaves index, its root
+    // the shadow rays' own world tree (hiprz_scene_host.cpp: build_shadow_tree): 64-byte walk records, the instance ids its leaves index, its root
     // (record 0) or RZ_END: none — the walks then take the reference's world tree
     const float4* shadow_nodes64;
     const uint32_t* shadow_order;
@@ -1025,7 +1025,7 @@ __device__ __forceinline__ int closest_hit_binned(const DScene& s, unsigned char
 // ---- MODE 3: nested walk on skip links with the top of every tree cached in LDS ----
 // For scenes whose records do not fit LDS (configs C, D) a segment is a chain of ~60-90 dependent node
 // fetches served by L2.  The device copy of the nodes is laid out breadth-first over ALL trees
-// (hiprz_api.hip: relayout), so the levels nearest the roots — the ones every ray visits — form a prefix;
+// (hiprz_scene_host.cpp: derive_tables), so the levels nearest the roots — the ones every ray visits — form a prefix;
 // each workgroup stages that prefix (nodes + links) into LDS.  Following skip links instead of popping a
 // stack means the walk needs no LDS stack at all, which is what frees the space for the cache.
 struct TopCache {

@@ -189,11 +189,12 @@ def test_engine_ray_casts_every_camera_after_each_frame(built):
     assert len(seen) >= 4                                           # walls, boxes, lamp: the pixels really look at different things
 
 
-def test_update_shading_equals_a_full_upload(built):
+@pytest.mark.parametrize("devices", [0, [0, 0]])
+def test_update_shading_equals_a_full_upload(built, devices):
     world = scenes.living_room(128, 80, 12)
     flat, cam = flatten(world), camera_struct(world.camera)
     cfg = RenderConfig(LightSampling(1, 1), Tracing(5, 4)).struct()
-    a = Context(0)
+    a = Context(devices)
     a.upload_scene(flat), a.upload_camera(cam), a.set_config(cfg)
     a.render(5)
     world.materials[1].color = (30, 200, 90, 255)            # the red wall turns green, the mirror rough, a light goes away

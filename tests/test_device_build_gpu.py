@@ -21,8 +21,8 @@ pytestmark = pytest.mark.gpu
 DEVICE, DEVICE_SAH = 2, 3   # HIPRZ_TREE_DEVICE (Morton order), HIPRZ_TREE_DEVICE_SAH (binned surface-area build)
 
 
-def _render(flat, cam, cfg, tree, passes=(1, 5, 4)):
-    c = Context(0)
+def _render(flat, cam, cfg, tree, passes=(1, 5, 4), devices=0):
+    c = Context(devices)
     c.set_tree(tree)
     c.upload_scene(flat), c.upload_camera(cam), c.set_config(cfg)
     for n in passes:
@@ -114,10 +114,11 @@ def test_device_built_world_tree_is_the_host_builders(built, n_instances):
     assert np.array_equal(order, flat.tlas_order)
 
 
+@pytest.mark.parametrize("devices", [0, [0, 0]])
 @pytest.mark.parametrize("device", [DEVICE, DEVICE_SAH])
-def test_refit_and_world_rebuild_equal_a_fresh_upload(built, device):
+def test_refit_and_world_rebuild_equal_a_fresh_upload(built, device, devices):
     """A mesh is deformed and an instance moved: hiprz_update_triangles + hiprz_update_instances on the device against a fresh upload of the
-    changed world (host trees)."""
+    changed world (host trees) — on one stream, and with a second stream on the same device that shares the scene copy."""
     def build(deformed):
         world = scenes.textured_sphere_scene(200, 120, resolution=96, map_size=64)
         if deformed:
@@ -130,7 +131,7 @@ def test_refit_and_world_rebuild_equal_a_fresh_upload(built, device):
     before, after = build(False), build(True)
     flat0, flat1, cam = flatten(before), flatten(after), camera_struct(before.camera)
     cfg = RenderConfig(tracing=Tracing(6, 4)).struct()
-    dev = _render(flat0, cam, cfg, device)
+    dev = _render(flat0, cam, cfg, device, devices=devices)
     # the changed triangles in the order they were uploaded in: a mesh's triangles are identified by their index before leaf reordering
     sphere = next(k for k, i in enumerate(before.instances) if i.name == "bugatti stand-in")
     def mesh_range(flat):
@@ -505,12 +506,13 @@ def test_engine_through_a_random_sequence_of_changes(built, seed, scene):
 
 
 @pytest.mark.parametrize("devices", [0, [0, 0]])
-@pytest.mark.parametrize("call", ["rebuild_trees", "update_instances"])
+@pytest.mark.parametrize("call", ["rebuild_trees", "update_instances", "upload_scene"])
 def test_a_refused_in_place_change_leaves_no_scene_behind(built, monkeypatch, devices, call):
     """hiprz_rebuild_trees and hiprz_update_instances rewrite node tables, triangle order and instance roots IN PLACE.  When the host then
     refuses to prove the device's output (here: on request — HIPRZ_TEST_REFUSE_TREES stands in for a tree the proof rejects), the call fails
     AND the context has no scene any more: the next render returns HIPRZ_ERR_STATE instead of walking tables nobody proved terminating — on
-    every stream that shares the device's scene copy — and a fresh upload brings the context back to the frame it rendered before."""
+    every stream that shares the device's scene copy — and a fresh upload brings the context back to the frame it rendered before.  A second
+    hiprz_upload_scene whose device build is refused has replaced the previous scene's buffers by then: it ends the same way."""
     from rayzath_amd._lib import HiprzError
     world = scenes.living_room(128, 80, 16)
     flat, cam = flatten(world), camera_struct(world.camera)
@@ -522,7 +524,8 @@ def test_a_refused_in_place_change_leaves_no_scene_behind(built, monkeypatch, de
     before = ctx.read_accum()
     monkeypatch.setenv("HIPRZ_TEST_REFUSE_TREES", "1")
     with pytest.raises(HiprzError) as e:
-        ctx.rebuild_trees(DEVICE_SAH) if call == "rebuild_trees" else ctx.update_instances(flat.instances)
+        {"rebuild_trees": lambda: ctx.rebuild_trees(DEVICE_SAH), "update_instances": lambda: ctx.update_instances(flat.instances),
+         "upload_scene": lambda: ctx.upload_scene(flat)}[call]()
     assert e.value.code == _abi.ERR_DEVICE and "refused" in str(e.value)
     monkeypatch.delenv("HIPRZ_TEST_REFUSE_TREES")
     for attempt in (lambda: ctx.render(1), lambda: ctx.ray_cast(10, 10), lambda: ctx.update_instances(flat.instances), lambda: ctx.rebuild_trees(DEVICE_SAH)):
@@ -532,6 +535,36 @@ def test_a_refused_in_place_change_leaves_no_scene_behind(built, monkeypatch, de
     ctx.upload_scene(flat)
     ctx.render(1), ctx.render(4)
     assert np.array_equal(ctx.read_accum(), before)
+    ctx.close()
+
+
+@pytest.mark.parametrize("devices", [0, [0, 0]])
+def test_an_upload_refused_by_validation_leaves_the_previous_scene_usable(built, devices):
+    """hiprz_upload_scene validates on the host before it touches a device buffer: a snapshot it refuses (HIPRZ_ERR_INVALID) changes
+    nothing — the previous scene renders the frame it rendered before, on every stream that shares the device's scene copy."""
+    from rayzath_amd._lib import HiprzError
+    world = scenes.living_room(128, 80, 16)
+    flat, cam = flatten(world), camera_struct(world.camera)
+    cfg = RenderConfig(LightSampling(1, 1), Tracing(5, 4)).struct()
+    ctx = Context(devices)
+    ctx.set_tree(DEVICE_SAH)
+    ctx.upload_scene(flat), ctx.upload_camera(cam), ctx.set_config(cfg)
+    ctx.render(1), ctx.render(4)
+    accum, depth, state = ctx.read_accum(), ctx.read_depth(), ctx.read_state()
+    order = flat.tlas_order.copy()
+    order[0] = len(flat.instances)
+    bad = FlatScene(nodes=flat.nodes, tlas_root=flat.tlas_root, tlas_order=order, tris=flat.tris, tri_attrs=flat.tri_attrs, instances=flat.instances,
+                    inst_materials=flat.inst_materials, materials=flat.materials, textures=flat.textures, texels=flat.texels,
+                    spot_lights=flat.spot_lights, direct_lights=flat.direct_lights)
+    with pytest.raises(HiprzError) as e:
+        ctx.upload_scene(bad)
+    assert e.value.code == _abi.ERR_INVALID, str(e.value)
+    ctx.reset()
+    ctx.render(1), ctx.render(4)
+    assert np.array_equal(ctx.read_accum(), accum) and np.array_equal(ctx.read_depth(), depth)
+    again = ctx.read_state()
+    for k in state:
+        assert np.array_equal(again[k], state[k]), k
     ctx.close()
 
 

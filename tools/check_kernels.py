@@ -65,6 +65,9 @@ def device_kernels(path):
         fat = os.path.join(tmp, "fatbin")
         # (an explicit output file: without one objcopy rewrites its INPUT in place — a new time stamp on the object, and for the library
         # exactly the in-place overwrite of a possibly mapped file that the Makefile's link-and-rename avoids)
+        # (a unit that defines no kernel has no such section and holds no kernels: rule 1 still catches a stub it should not have)
+        if ".hip_fatbin" not in run(os.path.join(LLVM, "llvm-readelf"), "-S", "-W", path):
+            return names
         subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", path, os.path.join(tmp, "discard")], check=True, capture_output=True)
         data = open(fat, "rb").read()
         # a linked library concatenates the units' bundles: split at the bundler's magic
