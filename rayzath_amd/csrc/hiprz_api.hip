@@ -224,8 +224,7 @@ void reproject_after_first_pass(hiprz_ctx* c, const DFrame& f, const hiprz_camer
     std::memcpy(prev.position, previous.position, 12), std::memcpy(prev.x_axis, previous.x_axis, 12);
     std::memcpy(prev.y_axis, previous.y_axis, 12), std::memcpy(prev.z_axis, previous.z_axis, 12);
     prev.tan_half_fov = previous.tan_half_fov, prev.aspect_ratio = previous.aspect_ratio;
-    const PassGeometry g = pass_geometry(c);
-    RZ_LAUNCH(rz_reproject_kernel, g.grid, dim3(256), 0, c->stream, f, c->dcamera, prev, c->prev_accum.ptr, c->prev_depth.ptr, c->temporal_blend);
+    RZ_LAUNCH(rz_reproject_kernel, dim3(c->plan.tile_grid), dim3(256), 0, c->stream, f, c->dcamera, prev, c->prev_accum.ptr, c->prev_depth.ptr, c->temporal_blend);
 }
 
 int allocate_frame(hiprz_ctx* c) {
@@ -292,24 +291,29 @@ int allocate_frame(hiprz_ctx* c) {
     return HIPRZ_OK;
 }
 
-bool resident_active(const hiprz_ctx* c) { return c->pipeline == 2; }
-
 }  // namespace
 
 namespace hiprz {
 
-// rays are reordered where the walk is bound by scattered fetches: scenes not staged in LDS, split pipeline
-bool sort_enabled(const hiprz_ctx* c) {
-    if (c->pipeline != 1 || c->sort_rays == 0) return false;
-    if (c->sort_rays == 1) return true;
-    // measured (1920x1080+, MODE 3; the sort itself costs ~0.12 ms per pass at 1080p): many small instances (config E, 46) 33.9 ->
-    // 26.5 ms per pass; one mid-size mesh (config C, 12 k nodes) trace kernel 853 -> 645 us, step 7.70 -> 6.98 ms; one big mesh
-    // (config D, 600 k nodes) trace kernel 2 656 -> 2 586 us but step 22.5 -> 23.2 ms.  So: on for many instances, and for trees
-    // small enough that a coherent wave finds its nodes in LDS / L2.
-    return !use_lds_scene(c) && effective_mode(c) >= 3 && (c->dscene.n_instances >= 16u || c->n_nodes <= kLatencyBoundNodes);
+// the only code that turns context fields into inputs of the launch plan (hiprz_plan.hpp)
+PlanInputs plan_inputs(const hiprz_ctx* c) {
+    PlanInputs in{};
+    in.pipeline_setting = c->pipeline_setting, in.traversal_mode = c->traversal_mode, in.lds_scene_override = c->lds_scene_override;
+    in.walk_order = c->walk_order, in.sort_rays = c->sort_rays, in.sort_bits = c->sort_bits, in.shadow_sort = c->shadow_sort;
+    in.shadow_packet = c->shadow_packet, in.defer_shadow_rays = c->defer_shadow_rays, in.nolight_kernels = c->nolight_kernels;
+    in.trace_waves = c->trace_waves, in.batch_waves = c->batch_waves, in.batch_segments = c->batch_segments;
+    in.wave_resident_max = c->wave_resident_max, in.xcd_swizzle = c->xcd_swizzle, in.heavy_first = c->heavy_first != 0, in.mode_flags = c->mode_flags;
+    in.spot_samples = c->config.spot_samples, in.direct_samples = c->config.direct_samples;
+    in.have_scene = c->have_scene, in.scene_tree = c->scene_tree, in.lds_scene = c->lds_scene, in.hot_bytes = c->dscene.hot_bytes;
+    in.stack_entries = c->stack_entries, in.world_stack_entries = c->dscene.world_stack_entries, in.mesh_stack_entries = c->dscene.mesh_stack_entries;
+    in.n_instances = c->dscene.n_instances, in.n_lights = c->dscene.n_spot_lights + c->dscene.n_direct_lights, in.n_textures = c->n_textures;
+    in.n_nodes = c->n_nodes, in.top_count = c->dscene.top_count, in.flat_world = c->flat_world;
+    in.have_camera = c->have_camera, in.n_local_tiles = c->n_local_tiles;
+    return in;
 }
 
 DFrame make_frame(hiprz_ctx* c, bool counted) {
+    const LaunchPlan& p = c->plan;
     DFrame f{};
     f.st0 = c->st0.ptr, f.st1 = c->st1.ptr, f.st2 = c->st2.ptr;
     f.accum = c->accum.ptr, f.depth = c->depth.ptr, f.rgba8 = c->rgba8.ptr;
@@ -318,17 +322,14 @@ DFrame make_frame(hiprz_ctx* c, bool counted) {
     f.counters = counted ? c->counters_dev.ptr : nullptr;
     f.tiles_x = c->tiles_x, f.rank = c->rank, f.world = c->world, f.n_local_tiles = c->n_local_tiles;
     f.xcd_swizzle = c->xcd_swizzle ? 1u : 0u;
-    f.nee = c->nee.ptr, f.nee_quads = 4u + 2u * (c->config.spot_samples + c->config.direct_samples);
-    const bool sorting = sort_enabled(c);
-    f.sort_key = sorting ? c->sort_keys.ptr : nullptr;
-    f.perm = sorting ? c->sort_perm.ptr : nullptr;
-    const bool shadow_sorting = sorting && c->shadow_sort != 0 && c->pipeline == 1 && defer_shadows(c);
-    f.shadow_key = shadow_sorting ? c->shadow_keys.ptr : nullptr;
-    f.shadow_perm = shadow_sorting ? c->shadow_perm.ptr : nullptr;
+    f.nee = c->nee.ptr, f.nee_quads = p.nee_quads;
+    f.sort_key = p.sort_enabled ? c->sort_keys.ptr : nullptr;
+    f.perm = p.sort_enabled ? c->sort_perm.ptr : nullptr;
+    f.shadow_key = p.shadow_sort ? c->shadow_keys.ptr : nullptr;
+    f.shadow_perm = p.shadow_sort ? c->shadow_perm.ptr : nullptr;
     // resident kernels: units by falling cost once an order for THIS kind of unit exists; costs are always collected (not while counting)
-    const uint32_t units = c->pipeline == 2 ? (wave_resident(c) ? c->n_local_tiles * 4u : c->n_local_tiles) : 0u;
-    f.unit_cost = c->heavy_first && units && !counted ? c->unit_cost.ptr : nullptr;
-    f.launch_order = c->heavy_first && units && !counted && c->order_units == units ? c->launch_order.ptr : nullptr;
+    f.unit_cost = p.heavy_units ? c->unit_cost.ptr : nullptr;
+    f.launch_order = p.heavy_units && c->order_units == p.heavy_units ? c->launch_order.ptr : nullptr;
     return f;
 }
 
@@ -336,79 +337,10 @@ DConfig make_config(const hiprz_ctx* c) {
     return DConfig{c->config.max_depth, c->config.spot_samples, c->config.direct_samples, c->config.seed, c->mode_flags};
 }
 
-// The binned walk pays off when a mesh visit is short and uniform (every mesh tree is a single leaf, e.g. the
-// Cornell configs: 329 vs 370 us per pass); with deep mesh trees a round lasts as long as its slowest item
-// and the nested walk is faster (config C: 1 668 vs 2 450 us).
-int effective_mode(const hiprz_ctx* c) {
-    if (c->scene_tree != HIPRZ_TREE_REFERENCE || (c->mode_flags & kIntegratorFlags)) return 3;  // (compat integrator: the cooperative walk, or the fused kernel's skip-link walk)  // rebuilt trees: the front-to-back cooperative walks only
-    if (c->traversal_mode >= 0) return c->traversal_mode;
-    // records do not fit LDS: skip-link walks in single-wave workgroups
-    if (!c->lds_scene && c->pipeline == 1) return 3;
-    return c->dscene.mesh_stack_entries <= 2u ? 2 : 1;
-}
-
-// Shadow rays get their own kernel when the scene has lights, is not staged in LDS (split pipeline) and the sample slots of a
-// segment fit the 30-bit mask of the hand-over record.
-bool defer_shadows(const hiprz_ctx* c) {
-    return c->defer_shadow_rays && c->pipeline == 1 && !use_lds_scene(c) && c->dscene.n_spot_lights + c->dscene.n_direct_lights != 0u &&
-           c->config.spot_samples + c->config.direct_samples <= 30u;
-}
-
-// the resident pipeline on a scene that is not staged in LDS: per-wave chains of passes (rz_wave_batch_kernel); needs the front-to-back
-// walk (mode 3) and a scene without lights (shadow rays are deferred to a kernel of their own otherwise)
-bool wave_resident(const hiprz_ctx* c) {
-    return c->pipeline == 2 && !use_lds_scene(c) && c->dscene.n_spot_lights + c->dscene.n_direct_lights == 0u && c->nolight_kernels && c->walk_order != 0 &&
-           (c->traversal_mode == -1 || c->traversal_mode == 3);
-}
-
 void resolve_pipeline(hiprz_ctx* c) {
     const int before = c->pipeline;
-    // a shard small enough to be ONE round of waves on the chip pays the slowest wave of every kernel of every pass in the split
-    // pipeline; without lights it runs per-wave chains of passes instead (hiprz_kernels.hpp: rz_wave_batch_kernel)
-    const bool dark_capable = c->have_scene && !use_lds_scene(c) && c->dscene.n_spot_lights + c->dscene.n_direct_lights == 0u && c->nolight_kernels && c->walk_order != 0 &&
-                              (c->traversal_mode == -1 || c->traversal_mode == 3);
-    const bool small_dark_shard = dark_capable && c->have_camera && c->n_local_tiles != 0u && c->n_local_tiles * 4u <= c->wave_resident_max;
-    if (c->mode_flags & kIntegratorFlags) c->pipeline = c->pipeline_setting == 0 ? 0 : 1;  // CUDA-compat integrator: split (sorted rays, cooperative walks, deferred shadow rays); 0 = one fused kernel per pass
-    else if (c->scene_tree != HIPRZ_TREE_REFERENCE)  // rebuilt trees: the front-to-back cooperative walks only (split, or per-wave resident)
-        c->pipeline = dark_capable && (c->pipeline_setting == 2 || (c->pipeline_setting < 0 && small_dark_shard)) ? 2 : 1;
-    else if (c->pipeline_setting >= 0) c->pipeline = c->pipeline_setting;
-    else if (small_dark_shard) c->pipeline = 2;
-    else {
-        // resident needs blob + walk workspace + 8 KiB of parked state per workgroup, four workgroups per CU
-        const size_t lds = size_t(c->dscene.hot_bytes) + size_t(c->stack_entries) * 1024u + BinnedLds::kFixedBytes + 8u * 1024u;
-        const bool mode_ok = c->traversal_mode == -1 || c->traversal_mode == 1 || c->traversal_mode == 2;  // walks the batch kernel has
-        c->pipeline = (c->have_scene && c->lds_scene && c->lds_scene_override != 0 && mode_ok && lds <= 40u * 1024u) ? 2 : 1;
-    }
+    c->pipeline = choose_pipeline(plan_inputs(c));
     if (c->pipeline != before) invalidate_graphs(c);
-}
-
-bool use_lds_scene(const hiprz_ctx* c) {
-    if (c->lds_scene_override == 0 || c->scene_tree != HIPRZ_TREE_REFERENCE || (c->mode_flags & kIntegratorFlags)) return false;
-    if (c->lds_scene_override == 1) return size_t(c->dscene.hot_bytes) + size_t(c->stack_entries) * 1024u <= 160u * 1024u;
-    return c->lds_scene;
-}
-
-
-// Two radix passes (16 key bits) are enough while a bin of the coarser order still holds a wave's worth of rays: up to ~2 M owned
-// pixels (config C: step 4.53 -> 4.33 ms, the sort 88 -> 59 us per pass).  Bigger frames and scenes with lights (whose shadow rays
-// follow a sorted order of their own) keep all 24 bits (config E: 16 bits 55.9 ms per step against 51.0).
-int effective_sort_bits(const hiprz_ctx* c) {
-    if (c->sort_bits > 0) return c->sort_bits;
-    const bool lights = c->dscene.n_spot_lights + c->dscene.n_direct_lights != 0u;
-    return (!lights && size_t(c->n_local_tiles) * 256u <= (size_t(32) << 16)) ? 16 : 24;
-}
-
-PassGeometry pass_geometry(const hiprz_ctx* c) {
-    PassGeometry g;
-    // with the XCD swizzle the grid is padded to a multiple of 8 workgroups (the extra ones find no tile)
-    g.grid = dim3(c->xcd_swizzle ? ((c->n_local_tiles + 7u) / 8u) * 8u : c->n_local_tiles), g.block = dim3(256);
-    g.lds_scene = use_lds_scene(c);
-    g.blob = g.lds_scene ? c->dscene.hot_bytes : 0u;
-    g.mode = effective_mode(c);
-    if (g.mode >= 3 && (g.lds_scene || (c->pipeline != 1 && !wave_resident(c)))) g.mode = 1;  // skip links are for scenes that are not staged whole: trace kernel, wave batch kernel
-    g.stack_lds = size_t(c->stack_entries) * 256u * sizeof(uint32_t);
-    g.walk_lds = g.mode == 2 ? size_t(BinnedLds::bytes_host(c->dscene.world_stack_entries, c->dscene.mesh_stack_entries)) : g.mode == 1 ? g.stack_lds : 0u;
-    return g;
 }
 
 }  // namespace hiprz
@@ -418,7 +350,7 @@ namespace {
 // one pass on the stream: trace + shade (split pipeline) or the fused kernel
 void launch_pass(hiprz_ctx* c, const DFrame& f, bool first, bool counted, hipEvent_t between_trace_and_shade = nullptr) {
     c->sorted_this_pass = false;
-    if (c->pipeline == 1 || wave_resident(c)) {  // (the first pass of a wave-resident frame: the split kernels)
+    if (c->plan.shade.active) {  // split pipeline, and the first pass of a wave-resident frame
         launch_trace(c, f, first, counted);
         if (between_trace_and_shade) (void)hipEventRecord(between_trace_and_shade, c->stream);
         launch_shade(c, f, first, counted);
@@ -436,7 +368,7 @@ void launch_resident(hiprz_ctx* c, const DFrame& f, uint32_t n, bool counted, hi
     // (and whenever the kind of unit changed) and refreshed every 64th batch — per-tile costs of a fixed view are stable, paths
     // regenerate at the same pixels — by one key kernel + a 24-bit radix sort of a few thousand keys on the render stream.
     if (f.unit_cost && n >= 2u) {
-        const uint32_t units = wave_resident(c) ? c->n_local_tiles * 4u : c->n_local_tiles;
+        const uint32_t units = c->plan.heavy_units;
         c->batches_since_order += 1u;
         if (c->order_units != units || c->batches_since_order >= 64u) {
             RZ_LAUNCH(rz_order_keys_kernel, dim3((units + 255u) / 256u), dim3(256), 0, c->stream, c->unit_cost.ptr, c->order_keys.ptr, units);
@@ -491,8 +423,8 @@ int finish_batch(hiprz_ctx* c, hipEvent_t e0, hipEvent_t e1, uint32_t n_passes, 
 }
 
 // What a captured batch depends on, byte for byte: the arguments every kernel of the batch receives by value (scene, camera, config and
-// frame views: raw pointers into buffers the context owns, sizes, sharding), the workspaces the sorts use, and every setting that
-// selects a kernel instantiation or a grid size.  The graph holds kernel nodes and event fork / join nodes only — no memset, memcpy or
+// frame views: raw pointers into buffers the context owns, sizes, sharding), the workspaces the sorts use, and the launch plan: every
+// kernel instantiation, grid and LDS size the batch's launches select.  The graph holds kernel nodes and event fork / join nodes only — no memset, memcpy or
 // library nodes, no host pointers — so "same key" means a replay does what an eager batch would do now.
 std::vector<unsigned char> graph_key_of(hiprz_ctx* c, const DFrame& f, uint32_t n_passes) {
     std::vector<unsigned char> key;
@@ -503,11 +435,29 @@ std::vector<unsigned char> graph_key_of(hiprz_ctx* c, const DFrame& f, uint32_t 
         const void* ptrs[5] = {t.keys_out.ptr, t.vals_a.ptr, t.vals_b.ptr, t.counts.ptr, t.row_total.ptr};
         put(ptrs, sizeof ptrs);
     }
-    const int settings[] = {c->pipeline, effective_mode(c), c->walk_order, c->trace_waves, int(c->scene_tree), effective_sort_bits(c), int(defer_shadows(c)), int(c->shadow_packet),
-                            int(use_lds_scene(c)), int(c->flat_world), c->nolight_kernels, int(c->n_textures), int(c->n_nodes), int(c->xcd_swizzle),
-                            int(sort_enabled(c)), c->shadow_sort, c->batch_waves, int(c->stack_entries), int(n_passes), int(c->n_local_tiles)};
-    put(settings, sizeof settings);
+    put(&c->plan, sizeof c->plan), put(&n_passes, sizeof n_passes);
     return key;
+}
+
+// the first pass of a restarted frame (renderFirstPass) with the reprojection of the frame it replaces; the caller advances the pass index
+void first_pass(hiprz_ctx* c, const DFrame& f, bool counted) {
+    const bool history = keep_history(c);
+    const hiprz_camera previous = c->frame_camera;
+    c->frame_camera = c->camera, c->frame_started = true;
+    RZ_LAUNCH(rz_pass_reset_kernel, dim3(1), dim3(1), 0, c->stream, c->pass_dev.ptr);
+    launch_pass(c, f, true, counted);
+    if (history) reproject_after_first_pass(c, f, previous);
+    c->reset_pending = false;
+    c->passes = 0;
+    c->ray_count = 0;
+}
+
+void grow_kernel_events(hiprz_ctx* c, size_t n) {
+    while (c->kernel_events.size() < n) {
+        hipEvent_t e = nullptr;
+        (void)hipEventCreate(&e);
+        c->kernel_events.push_back(e);
+    }
 }
 
 int render_passes(hiprz_ctx* c, uint32_t n_passes, bool counted) {
@@ -519,10 +469,11 @@ int render_passes(hiprz_ctx* c, uint32_t n_passes, bool counted) {
     }
     resolve_pipeline(c);  // the choice depends on the selected camera's shard size too
     StageTimer timer;
-    if (defer_shadows(c)) {  // hand-over buffers of the deferred shadow rays: (4 + 2 * samples) float4 per owned pixel
-        const size_t n = size_t(c->n_local_tiles) * 256u, k = c->config.spot_samples + c->config.direct_samples;
-        if (c->nee.count < n * (4u + 2u * k)) c->graph_valid = false;
-        RZ_HIP(c, c->nee.resize(n * (4u + 2u * k)));
+    c->plan = plan_launches(plan_inputs(c), counted);
+    if (c->plan.defer_shadows) {  // hand-over buffers of the deferred shadow rays: (4 + 2 * samples) float4 per owned pixel
+        const size_t n = size_t(c->n_local_tiles) * 256u * c->plan.nee_quads;
+        if (c->nee.count < n) c->graph_valid = false;
+        RZ_HIP(c, c->nee.resize(n));
     }
     const DFrame f = make_frame(c, counted);
     if (!f.perm) c->perm_valid = false;                                        // passes without reordering leave the order behind
@@ -533,27 +484,17 @@ int render_passes(hiprz_ctx* c, uint32_t n_passes, bool counted) {
     if (c->pipeline == 2) {
         uint32_t remaining = n_passes;
         if (c->reset_pending) {  // renderFirstPass: the fused kernel
-            const bool history = keep_history(c);
-            const hiprz_camera previous = c->frame_camera;
-            c->frame_camera = c->camera, c->frame_started = true;
-            RZ_LAUNCH(rz_pass_reset_kernel, dim3(1), dim3(1), 0, c->stream, c->pass_dev.ptr);
-            launch_pass(c, f, true, counted);
-            if (history) reproject_after_first_pass(c, f, previous);
+            first_pass(c, f, counted);
             RZ_LAUNCH(rz_pass_update_kernel, dim3(1), dim3(1), 0, c->stream, c->pass_dev.ptr);
-            c->reset_pending = false;
-            c->passes = 1;
-            c->ray_count = c->owned_pixels;
+            c->passes += 1;
+            c->ray_count += c->owned_pixels;
             remaining -= 1u;
         }
         if (remaining) {
             c->kernel_event_passes = 0;
             if (counted) launch_resident(c, f, remaining, true);
             else if (c->time_kernels) {  // bench.py's roofline: the batch kernel's own duration
-                while (c->kernel_events.size() < 3u) {
-                    hipEvent_t e = nullptr;
-                    (void)hipEventCreate(&e);
-                    c->kernel_events.push_back(e);
-                }
+                grow_kernel_events(c, 3u);
                 launch_resident(c, f, remaining, false, c->kernel_events[0], c->kernel_events[1]);
                 c->kernel_event_passes = remaining;
             } else launch_resident(c, f, remaining, false);
@@ -595,11 +536,7 @@ int render_passes(hiprz_ctx* c, uint32_t n_passes, bool counted) {
     // eagerly.
     const bool timed = c->time_kernels && c->pipeline == 1 && !counted && !c->reset_pending;
     if (timed) {
-        while (c->kernel_events.size() < size_t(3 * n_passes)) {
-            hipEvent_t e = nullptr;
-            (void)hipEventCreate(&e);
-            c->kernel_events.push_back(e);
-        }
+        grow_kernel_events(c, 3u * size_t(n_passes));
         c->kernel_event_passes = n_passes;
     }
     for (uint32_t i = 0; i < n_passes; ++i) {
@@ -613,19 +550,8 @@ int render_passes(hiprz_ctx* c, uint32_t n_passes, bool counted) {
             c->ray_count += c->owned_pixels;
             continue;
         }
-        if (c->reset_pending) {
-            const bool history = keep_history(c);
-            const hiprz_camera previous = c->frame_camera;
-            c->frame_camera = c->camera, c->frame_started = true;
-            RZ_LAUNCH(rz_pass_reset_kernel, dim3(1), dim3(1), 0, c->stream, c->pass_dev.ptr);
-            launch_pass(c, f, true, counted);
-            if (history) reproject_after_first_pass(c, f, previous);
-            c->reset_pending = false;
-            c->passes = 0;
-            c->ray_count = 0;
-        } else {
-            launch_pass(c, f, false, counted);
-        }
+        if (c->reset_pending) first_pass(c, f, counted);
+        else launch_pass(c, f, false, counted);
         launch_sort(c);
         RZ_LAUNCH(rz_pass_update_kernel, dim3(1), dim3(1), 0, c->stream, c->pass_dev.ptr);
         c->passes += 1;
@@ -1049,7 +975,7 @@ int hiprz_pipeline(hiprz_ctx* c, int* out) {
 
 int hiprz_traversal_mode(hiprz_ctx* c, int* out) {
     if (!c || !out) return HIPRZ_ERR_INVALID;
-    *out = effective_mode(c);
+    *out = int(plan_launches(plan_inputs(c), false).reported_mode);
     return HIPRZ_OK;
 }
 
@@ -1204,7 +1130,7 @@ int hiprz_kernel_breakdown_ms(hiprz_ctx* c, double* trace_ms, double* shade_ms, 
     RZ_HIP(c, hipStreamSynchronize(c->stream));
     *trace_ms = *shade_ms = 0.0;
     *passes = 0;
-    if (resident_active(c)) {  // one launch for all the passes of the batch: reported as "trace"
+    if (c->pipeline == 2) {  // one launch for all the passes of the batch: reported as "trace"
         if (c->kernel_event_passes) {
             float a = 0;
             RZ_HIP(c, hipEventElapsedTime(&a, c->kernel_events[0], c->kernel_events[1]));

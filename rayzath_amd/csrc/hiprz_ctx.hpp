@@ -1,7 +1,7 @@
 // hiprz_ctx.hpp — host-side state of a context (struct hiprz_ctx) and what the translation units of libhiprz.so share:
 // hiprz_api.hip (context life cycle, settings, the render loop), hiprz_scene.hip (scene upload and updates; its pure-host half is
 // hiprz_scene_host.cpp), hiprz_readback.hip (parts -> frame: tone map, assembly, reads, tile export, present), hiprz_launch_*.hip (the
-// pass kernels' instantiations and their launch logic), hiprz_sort.hip (ray reordering), hiprz_build.hip (trees built on the device)
+// pass kernels' instantiations, dispatched on the launch plan of the pure-host hiprz_plan.cpp), hiprz_sort.hip (ray reordering), hiprz_build.hip (trees built on the device)
 // and hiprz_denoise.hip (denoising).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 
 #include "hiprz.h"
 #include "hiprz_device.hpp"
+#include "hiprz_plan.hpp"
 #include "hiprz_scene_host.hpp"  // DeviceMesh
 
 namespace hiprz {
@@ -105,13 +106,12 @@ struct PartCopy {  // one copy of a push
 
 }  // namespace hiprz
 
+using hiprz::kIntegratorFlags;
+
 // What belongs to ONE camera of the world: its record, the per-pixel path state and accumulators, the device-resident pass index, the
 // ray-order and shadow hand-over buffers sized for its resolution, the graph that was captured over these pointers.  The reference
 // renders every enabled camera per call (cpu_engine_renderer.cpp:97-117); a context keeps one of these per camera and the calls
 // address the selected one (hiprz_select_camera): hiprz_ctx IS-A frame state, the others are parked.
-// the HIPRZ_COMPAT_* flags that change the integration (everything but the reprojection of history at a restart)
-constexpr uint32_t kIntegratorFlags = HIPRZ_MODE_CUDA_COMPAT & ~HIPRZ_COMPAT_REPROJECTION;
-
 struct hiprz_frame_state {
     hiprz_camera camera{};
     hiprz::DCamera dcamera{};
@@ -245,19 +245,10 @@ struct hiprz_ctx : hiprz_frame_state {
     int lds_scene_override = -1; // -1 auto, 0 never, 1 always (if it fits at all)
 
     uint32_t rank = 0, world = 1;  // the shard this context renders
-    // 0 fused (one kernel per pass), 1 split (trace kernel -> shade kernel per pass), 2 resident (one kernel per batch
-    // of passes).  -1: resident when the scene is staged in LDS (config B: as fast as split on a whole frame, 2.26 ms per
-    // 8 passes, and 0.34 vs 0.45 ms on an eighth of it — per-pass launch/ramp/tail costs vanish), else split (10-20 % faster
-    // than fused on configs C, D; the resident kernel has no LDS room for the tree-top cache).
-    int pipeline_setting = -1;
+    int pipeline_setting = -1;  // hiprz_set_pipeline: -1 = per scene (hiprz_plan.cpp: choose_pipeline)
     int pipeline = 1;  // resolved by resolve_pipeline() at upload / set time and before a render call
-    uint32_t wave_resident_max = 1u << 30;  // HIPRZ_WAVE_RESIDENT_MAX: scenes without lights that are not staged in LDS run the resident pipeline
-                                         // (rz_wave_batch_kernel) while a shard has at most this many waves — no limit since the end of round 3.
-                                         // Measured on MI355X, split / resident, ms per step of 8 passes: an eighth of a 1080p frame C 1.18 /
-                                         // 0.61, D 3.78 / 2.69; half C 2.46 / 1.86, D 5.79 / 3.91; a whole frame (32 400 waves), since the walk's
-                                         // instance level: C 3.69 / 3.38, D 7.28 / 7.19 (it was C 3.78 / 3.82 before); a 4K frame (129 600 waves):
-                                         // C 14.26 / 12.73, D 27.26 / 27.18.  (The kernel keeps the register budget of 4 waves per SIMD: with 5 — what
-                                         // D's trace kernel likes — the shading spills: D 7.18 -> 7.51, C 3.38 -> 3.81 ms per step.)
+    hiprz::LaunchPlan plan{};  // of the render call being enqueued (render_passes): what every launch of it selects
+    uint32_t wave_resident_max = 1u << 30;  // HIPRZ_WAVE_RESIDENT_MAX (hiprz_plan.cpp: choose_pipeline)
     // device-built trees (hiprz_set_tree(HIPRZ_TREE_DEVICE), hiprz_build.hip): the 32-byte node records of the whole scene in a buffer of
     // their own (the hot blob's node section only holds the uploaded prefix), the workspaces of build and refit, the meshes
     hiprz::DeviceArray<uint8_t> dev_nodes, has_mesh, build_temp;
@@ -275,7 +266,7 @@ struct hiprz_ctx : hiprz_frame_state {
     hiprz::DeviceArray<int32_t> pick_dev;
 
     hiprz_config config{8u, 8u, 1u, 1u, 20240501u};
-    int traversal_mode = -1;  // -1 = choose per scene (effective_mode)
+    int traversal_mode = -1;  // -1 = choose per scene (hiprz_plan.cpp)
     uint32_t tree_mode = 0;   // HIPRZ_TREE_* (hiprz_set_tree), applied by hiprz_upload_scene
     uint32_t scene_tree = 0;  // ... of the scene that is uploaded now
     bool device_sah = false;  // HIPRZ_TREE_DEVICE_SAH: the device's mesh trees by the binned surface-area build instead of Morton order
@@ -395,48 +386,20 @@ inline int mark_consumed(hiprz_ctx* head, PartStaging& staging) {
     return HIPRZ_OK;
 }
 
-constexpr uint32_t kLatencyBoundNodes = 32768u;  // trees beyond ~1 MiB of nodes: fetches come from L2 / HBM, occupancy hides them
-constexpr uint32_t kTopCacheNodes = 682u;        // 682 x 36 B = 24 KiB per workgroup: ~9 levels of every tree, 5 workgroups per CU
 constexpr size_t kLdsSceneLimit = 52u * 1024u;   // per workgroup: 3 x 52 KiB < 160 KiB per CU
 
-// choices derived from the context's settings and the uploaded scene (hiprz_api.hip)
+// choices derived from the context's settings and the uploaded scene: hiprz_plan.hpp; hiprz_api.hip fills its inputs from a context
 void invalidate_graphs(hiprz_ctx* c);  // of every camera: settings and the scene are shared by the cameras of a context
 void resolve_pipeline(hiprz_ctx* c);   // reads the uploaded scene's fields: whoever changes them calls it
-int effective_mode(const hiprz_ctx* c);
-bool defer_shadows(const hiprz_ctx* c);
-bool use_lds_scene(const hiprz_ctx* c);
-bool sort_enabled(const hiprz_ctx* c);
-bool wave_resident(const hiprz_ctx* c);  // resident pipeline on a scene that is not staged in LDS: rz_wave_batch_kernel
-int effective_sort_bits(const hiprz_ctx* c);
 DConfig make_config(const hiprz_ctx* c);
-// launch geometry of the 256-thread pass kernels: one workgroup per owned 32x8 tile
-struct PassGeometry {
-    dim3 grid, block;
-    bool lds_scene;    // the hot blob is staged into LDS by every workgroup
-    size_t blob;       // its bytes (0 when not staged)
-    int mode;          // walk of this launch: 1 LDS stack, 2 workgroup-binned, 3 skip links (split pipeline, global scene)
-    size_t stack_lds;  // LDS stack columns of the MODE 1 walk (and of inline shadow rays)
-    size_t walk_lds;   // workspace of the closest-hit walk
-};
-PassGeometry pass_geometry(const hiprz_ctx* c);
 
-// launch units.  `first`: renderFirstPass instead of renderCumulativePass; `counted`: the instrumented instantiation.
+// launch units: each dispatches on c->plan.  `first`: renderFirstPass instead of renderCumulativePass; `counted`: the instrumented instantiation.
 void launch_trace(hiprz_ctx* c, const DFrame& f, bool first, bool counted);   // split pipeline: closest-hit walk -> hit records
 void launch_shade(hiprz_ctx* c, const DFrame& f, bool first, bool counted);   // split pipeline: shading (+ deferred shadow rays and their sorts)
 void launch_fused(hiprz_ctx* c, const DFrame& f, bool first, bool counted);   // fused pipeline: one kernel per pass
 void launch_batch(hiprz_ctx* c, const DFrame& f, uint32_t n_passes, bool counted, hipEvent_t before, hipEvent_t after);  // resident pipeline
-// the resident batch kernel's instantiation and launch geometry as launch_batch chose them
-struct BatchVariant {
-    int mode;             // 1 LDS stack, 2 workgroup-binned, 4 binned with the one-leaf world
-    bool lds_scene;       // the hot blob is staged into LDS
-    int shading;          // 1 general, RZ_SHADOW_NONE, RZ_SHADOW_PLAIN
-    bool five;            // the 5-wave build (plain shading only)
-    uint32_t units;       // tiles of the (swizzle-padded) grid
-    size_t lds;           // dynamic LDS per workgroup
-    uint32_t park_offset; // where the parked state starts behind the scene blob
-};
-// hiprz_launch_batch_seg.hip: the batch with every tile's passes cut into `segments` self-scheduled segments (rz_batch_seg_kernel)
-void launch_batch_segmented(hiprz_ctx* c, const DFrame& f, uint32_t n_passes, uint32_t segments, bool counted, const BatchVariant& v);
+// hiprz_launch_batch_seg.hip: the batch (c->plan.batch) with every tile's passes cut into `segments` self-scheduled segments (rz_batch_seg_kernel)
+void launch_batch_segmented(hiprz_ctx* c, const DFrame& f, uint32_t n_passes, uint32_t segments, bool counted);
 void launch_sort(hiprz_ctx* c, bool beside = false);  // keys of the next rays -> the permutation the next trace kernel follows;
                                                       // beside: on the auxiliary stream, joined by join_sort()
 void join_sort(hiprz_ctx* c);

@@ -13,6 +13,7 @@
 
 #include "hiprz.h"
 #include "hiprz_end.hpp"
+#include "hiprz_lds.hpp"
 #include "hiprz_shard.hpp"
 
 namespace hiprz {
@@ -27,9 +28,6 @@ namespace hiprz {
 #endif
 #ifndef RZ_BATCH_SHARED_RCP   // ... in the resident pipeline's batch kernel
 #define RZ_BATCH_SHARED_RCP 1
-#endif
-#ifndef RZ_MIN_WAVES
-#define RZ_MIN_WAVES 4
 #endif
 #ifndef RZ_TRACE_MIN_WAVES
 #define RZ_TRACE_MIN_WAVES 5
@@ -736,9 +734,9 @@ struct BinnedLds {  // per-workgroup workspace carved from dynamic LDS (256 lane
     uint32_t* items;    // [256]     instance << 8 | source lane
     uint32_t* bins;     // [2][64] per-instance item counts, double-buffered by round
     uint32_t* stacks;   // [(world + mesh entries)][256] level-major stack columns
-    static constexpr uint32_t kFixedBytes = 15u * 1024u;
+    static constexpr uint32_t kFixedBytes = kBinnedFixedBytes;
     static __host__ uint32_t bytes_host(uint32_t world_entries, uint32_t mesh_entries) {
-        return kFixedBytes + (world_entries + mesh_entries) * 1024u;
+        return kFixedBytes + (world_entries + mesh_entries) * kBinnedEntryBytes;
     }
     __device__ __forceinline__ explicit BinnedLds(unsigned char* base) {
         ray = reinterpret_cast<float*>(base);
@@ -1032,7 +1030,7 @@ struct TopCache {
     const float4* nodes;   // LDS: top_count x 2 float4
     const uint32_t* skip;  // LDS: top_count
     uint32_t count;
-    static __host__ uint32_t bytes_host(uint32_t top_count) { return top_count * 36u; }
+    static __host__ uint32_t bytes_host(uint32_t top_count) { return top_count * kTopNodeBytes; }
 };
 // Front-to-back mesh walk.  The reference visits a node's first child, then its second (cpu_engine_kernel.cpp:331-352);
 // its builder puts the centroids BELOW the split plane into the first child (bvh_tree_node.hpp:150-215), so that fixed order is
@@ -1199,7 +1197,8 @@ struct CoopLds {  // LDS-qualified pointers: ds_read / ds_write, not flat access
     RZ_LDS f4* res;       // [128]    by entry: bits(t) or ~0 = no hit, bits(triangle | external << 31), b1, b2
     // R: the winner's position in the reference's leaf order, written by the winning tester after the entry's four lanes have read the
     // record (one wave: LDS operations complete in issue order).  8 KiB per wave: twenty single-wave workgroups fill a CU's 160 KiB.
-    static constexpr uint32_t kEntries = 128u, kBytes = 4u * kEntries * 16u;
+    static constexpr uint32_t kEntries = 128u, kBytes = kCoopLdsBytes;
+    static_assert(kBytes == 4u * kEntries * 16u, "rec [3][128] + res [128] float4");
     RZ_DEV explicit CoopLds(unsigned char* base) : rec((RZ_LDS f4*)base), res((RZ_LDS f4*)(base + 3u * kEntries * 16u)) {}
     RZ_DEV RZ_LDS uint32_t* ref(uint32_t e) const { return (RZ_LDS uint32_t*)(rec + 2u * kEntries + e) + 3; }
 };
@@ -1703,6 +1702,7 @@ RZ_DEV float any_hit_coop(const DScene& s, const CoopLds& lds, bool active, cons
 // to rounding.
 template <bool COUNT, bool RCP, bool MASK = false>
 RZ_DEV col4 any_hit_packet(const DScene& s, RZ_LDS f4* rays, bool active, const Ray& ray, bool filtering, Counters& cnt) {
+    static_assert(kPacketLdsBytes == 2u * 64u * sizeof(f4) && kPacketMaskLdsBytes == 3u * 64u * sizeof(f4), "rays [2][64], MASK: + colours [64]");
     const bool scene_fast = s.fast_div != 0u;
     WalkRay g;
     g.o = ray.o, g.d = ray.d, g.near_ = ray.near_, g.far_ = ray.far_;
@@ -1859,22 +1859,18 @@ RZ_DEV int closest_hit(const DScene& s, uint32_t* lds_column, Ray& ray, Hit& hit
     if (s.n_instances == 0) return 0;
     return closest_hit_stack<COUNT, RCP>(s, lds_column, ray, hit, cnt);  // MODE 2 calls closest_hit_binned directly
 }
-// what a shadow-ray walk needs besides the scene: the lane's LDS stack column (MODE 1) or the staged tree tops (MODE 3)
+// what a shadow-ray walk needs besides the scene: the lane's LDS stack column (MODE 1) or the staged tree tops (MODE 3); the further
+// modes are the RZ_SHADOW_* ids of hiprz_lds.hpp —
 // MODE 4 ("defer"): no walk here — the sample's shadow ray and its unshadowed radiance term are written out for
 // rz_shadow_kernel, which walks the rays of all pixels in a lean kernel of its own and finishes the sums in this order.
-#define RZ_SHADOW_DEFER 4
 // MODE 5 ("none"): instantiation for scenes WITHOUT lights — directIllumination returns 0 there before it evaluates anything
 // (cpu_engine_kernel.cpp:703, :758), so the whole next-event-estimation code (and its registers) is compiled out.
-#define RZ_SHADOW_NONE 5
 // MODE 6 ("plain"): no lights AND no maps of any kind in the scene — texture fetches, normal mapping and the sky's texture
 // coordinates are compiled out as well.
-#define RZ_SHADOW_PLAIN 6
 // MODE 8 ("compat"): the CUDA engine's behaviours selected by DConfig::flags (hiprz_compat.hpp): shadow rays inline on skip links,
 // opaque as in the CPU kernel or — HIPRZ_COMPAT_SHADOW_COLOR — through triangles with a coloured mask.
-#define RZ_SHADOW_COMPAT 8
 // MODE 9: the compat shading with the shadow rays DEFERRED like MODE 4 (the opaque shadow rays of the CPU kernel; the coloured mask of
 // HIPRZ_COMPAT_SHADOW_COLOR needs a texture fetch per crossed triangle and stays inline, MODE 8)
-#define RZ_SHADOW_COMPAT_DEFER 9
 constexpr bool shadow_mode_defers(int mode) { return mode == RZ_SHADOW_DEFER || mode == RZ_SHADOW_COMPAT_DEFER; }
 constexpr bool shadow_mode_compat(int mode) { return mode == RZ_SHADOW_COMPAT || mode == RZ_SHADOW_COMPAT_DEFER; }
 template <bool COUNT>

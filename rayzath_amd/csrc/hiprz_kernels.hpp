@@ -323,7 +323,8 @@ __global__ void __launch_bounds__(256, RZ_MIN_WAVES) rz_pass_kernel(const DScene
     Hit hit;
     int found;
     if constexpr (binned_mode(MODE)) {  // what the walk does not read is parked in LDS meanwhile
-        // 4 KiB behind the binned walk's workspace (launch_pass adds them to the fused kernel's LDS size)
+        // 4 KiB behind the binned walk's workspace (the launch plan adds them to the fused kernel's LDS size)
+        static_assert(kFusedParkBytes == 4u * 256u * sizeof(uint32_t), "park [4][256]");
         uint32_t* park = reinterpret_cast<uint32_t*>(workspace + BinnedLds::kFixedBytes + (s.world_stack_entries + s.mesh_stack_entries) * 1024u);
         park[0 * 256 + threadIdx.x] = __float_as_uint(ps.color.r), park[1 * 256 + threadIdx.x] = __float_as_uint(ps.color.g);
         park[2 * 256 + threadIdx.x] = __float_as_uint(ps.color.b), park[3 * 256 + threadIdx.x] = ps.material | (ps.depth << 16);

@@ -27,7 +27,7 @@ void launch_seg(hiprz_ctx* c, const DFrame& f, uint32_t n, uint32_t segments, co
 
 template <bool COUNT, int M, bool L>
 void launch_seg_shading(hiprz_ctx* c, const DFrame& f, uint32_t n, uint32_t segments, const BatchVariant& v) {
-    if (v.shading == RZ_SHADOW_PLAIN && v.five) launch_seg<COUNT, M, L, RZ_SHADOW_PLAIN, 5>(c, f, n, segments, v);
+    if (v.five) launch_seg<COUNT, M, L, RZ_SHADOW_PLAIN, 5>(c, f, n, segments, v);
     else if (v.shading == RZ_SHADOW_PLAIN) launch_seg<COUNT, M, L, RZ_SHADOW_PLAIN, RZ_MIN_WAVES>(c, f, n, segments, v);
     else if (v.shading == RZ_SHADOW_NONE) launch_seg<COUNT, M, L, RZ_SHADOW_NONE, RZ_MIN_WAVES>(c, f, n, segments, v);
     else launch_seg<COUNT, M, L, 1, RZ_MIN_WAVES>(c, f, n, segments, v);
@@ -44,8 +44,8 @@ void launch_seg_t(hiprz_ctx* c, const DFrame& f, uint32_t n, uint32_t segments, 
 
 }  // namespace
 
-void launch_batch_segmented(hiprz_ctx* c, const DFrame& f, uint32_t n_passes, uint32_t segments, bool counted, const BatchVariant& v) {
-    counted ? launch_seg_t<true>(c, f, n_passes, segments, v) : launch_seg_t<false>(c, f, n_passes, segments, v);
+void launch_batch_segmented(hiprz_ctx* c, const DFrame& f, uint32_t n_passes, uint32_t segments, bool counted) {
+    counted ? launch_seg_t<true>(c, f, n_passes, segments, c->plan.batch) : launch_seg_t<false>(c, f, n_passes, segments, c->plan.batch);
 }
 
 }  // namespace hiprz

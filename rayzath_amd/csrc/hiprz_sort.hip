@@ -198,7 +198,7 @@ void radix_sort_n(hipStream_t stream, uint32_t* keys, uint32_t n, uint32_t first
     }
 }
 void radix_sort(hiprz_ctx* c, uint32_t* keys, uint32_t* perm, hiprz_frame_state::SortTemp& t, hipStream_t stream) {
-    const int passes = (effective_sort_bits(c) + 7) / 8;
+    const int passes = (int(c->plan.sort_bits) + 7) / 8;
     radix_sort_n(stream, keys, c->n_local_tiles * 256u, uint32_t(24 - 8 * passes), passes, perm, nullptr, t);
 }
 
@@ -230,7 +230,7 @@ void sort_u32(hipStream_t stream, uint32_t* keys, uint32_t n, int key_bits, uint
 // main stream has been given so far — the deferred shadow-ray kernel that follows on the main stream does not need this order, and
 // the sort's small, bandwidth-light kernels fit beside its VALU-bound walk; join_sort() makes the main stream wait for it.
 void launch_sort(hiprz_ctx* c, bool beside) {
-    if (!sort_enabled(c) || c->n_local_tiles == 0 || c->sorted_this_pass) return;
+    if (!c->plan.sort_enabled || c->n_local_tiles == 0 || c->sorted_this_pass) return;
     c->sorted_this_pass = true;
     if (beside && c->aux_stream) {
         (void)hipEventRecord(c->aux_fork, c->stream);
