@@ -16,9 +16,11 @@
 #include "hiprz_lds.hpp"
 #include "hiprz_shard.hpp"
 
+#define RZ_DEV __device__ __forceinline__
+#include "hiprz_flat_pick.hpp"
+
 namespace hiprz {
 
-#define RZ_DEV __device__ __forceinline__
 // experiment knobs (tools/ab_variants.sh builds one library per setting)
 #ifndef RZ_FUSED_SHARED_RCP   // packed shared-reciprocal box test in the fused pass kernel's closest-hit walk
 #define RZ_FUSED_SHARED_RCP 0
@@ -747,33 +749,138 @@ struct BinnedLds {  // per-workgroup workspace carved from dynamic LDS (256 lane
     }
 };
 
+// What the one-leaf walk needs of the scene and of nothing else: built once per tile (or launch), not once per pass.  Every field is
+// the same in all lanes and is held as a scalar (readfirstlane), so `k < count` below is a scalar branch and not eight lane masks.
+struct FlatWorld {
+    float4 root0, root1;  // the world tree's root record: the leaf's box
+    uint32_t ids;         // the leaf's instance ids in leaf order, 4 bits each (flat_pack_id)
+    uint32_t count;       // instances in the leaf (<= 8)
+    uint32_t wide;        // bit i: instance i's mesh is one leaf of more than 4 triangles — its visits are shared by 8 lanes
+};
+RZ_DEV uint32_t wave_uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
+RZ_DEV float wave_uniform(float v) { return __uint_as_float(wave_uniform(__float_as_uint(v))); }
+RZ_DEV float4 wave_uniform(float4 v) { return make_float4(wave_uniform(v.x), wave_uniform(v.y), wave_uniform(v.z), wave_uniform(v.w)); }
+// Must be reached by whole waves (a ballot).  The scene is staged in LDS: every read here is an LDS read.
+RZ_DEV FlatWorld make_flat_world(const DScene& s) {
+    FlatWorld fw;
+    fw.root0 = fw.root1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    fw.ids = fw.count = fw.wide = 0u;
+    if (s.n_instances == 0) return fw;  // uniform
+    fw.root0 = wave_uniform(s.nodes[2 * s.tlas_root]), fw.root1 = wave_uniform(s.nodes[2 * s.tlas_root + 1]);
+    const uint32_t begin = __float_as_uint(fw.root1.z);
+    fw.count = __float_as_uint(fw.root1.w) & HIPRZ_NODE_COUNT_MASK;
+    if (fw.count > 8u) fw.count = 8u;  // (the host selects this walk for leaves of at most 8 only)
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; ++k)
+        if (k < fw.count) fw.ids = flat_pack_id(fw.ids, k, wave_uniform(s.tlas_order[begin + k]));
+    // Visits of a mesh that is ONE leaf of more than 4 triangles (a Cornell cube: 12) are shared by 8 lanes (closest_hit_binned)
+    const uint32_t i = threadIdx.x & 63u;
+    bool wide = false;
+    if (i < s.n_instances && i < 8u) {
+        const uint32_t root = __float_as_uint(s.instances[7 * i].w);
+        const uint32_t meta = __float_as_uint(s.nodes[2 * root + 1].w);
+        wide = (meta & HIPRZ_NODE_LEAF) != 0u && (meta & HIPRZ_NODE_COUNT_MASK) > 4u;
+    }
+    fw.wide = uint32_t(__ballot(wide)) & 0xFFu;
+    return fw;
+}
+
 // Worlds whose tree is ONE leaf (up to 8 instances: a Cornell box).  The reference tests every instance box of a leaf, one after the
 // other, each against the range as it is when the walk gets there (cpu_engine_kernel.cpp:299-305).  Only `tmin > far` depends on
 // what was hit before, and `tmax < near` on a near end that moves by a rounding at most (a hit rescales it through the instance's
 // length factor and back): so all the boxes are tested ONCE, up front, at full lane utilisation — bit k of the mask = "tmax >= near
-// and tmin <= tmax", tm[k] = tmin — and a round only compares tm[k] with the far end as it is then.  The same verdicts as the
-// one-by-one walk, the same count of box tests; the divergent per-lane search of the next candidate (a wave iterates as often as
-// its slowest lane) becomes eight uniform tests and a few compares per round.
+// and tmin <= tmax", tm[k] = tmin — and a round only compares tm[k] with the far end as it is then (flat_pick).  The same verdicts as
+// the one-by-one walk, the same count of box tests.  tm[k] of a slot whose bit is clear is never looked at.
 template <bool COUNT, bool RCP>
-RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, uint32_t begin, uint32_t count, uint32_t from_k, const WalkRay& g, float (&tm)[8], bool counting, Counters& cnt) {
+RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, const WalkRay& g, float (&tm)[8], bool counting, Counters& cnt) {
     uint32_t mask = 0u;
 #pragma unroll
     for (uint32_t k = 0; k < 8u; ++k) {
-        if (k < count && k >= from_k) {
+        tm[k] = 0.0f;
+        if (k < fw.count) {  // scalar
             float4 ib0, ib1;
-            load_instance_box(s, s.tlas_order[begin + k], ib0, ib1);
+            load_instance_box(s, flat_id(fw.ids, k), ib0, ib1);
             float tmin, tmax;
             box_range_unpacked<RCP>(ib0, ib1, g, tmin, tmax);
             if (counting) { RZ_PHASE(1); RZ_COUNT(box_tests); }
-            if (!(tmax < g.near_ || tmin > tmax)) mask |= 1u << k, tm[k] = tmin;
+            mask |= uint32_t(!(tmax < g.near_ || tmin > tmax)) << k;
+            tm[k] = tmin;
         }
     }
     return mask;
 }
 
+// C of a binned round for closest_hit_flat: the lane that holds dense item `slot` enters the item's instance for the item's ray.
+// closest_hit_binned keeps its own copy of these lines in place: called from here its code came out of the compiler in another
+// order, and the general walk's kernels are to stay the instructions they were.
+template <bool COUNT, bool RCP>
+RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_column, bool scene_fast, uint32_t slot, Counters& cnt) {
+    RZ_PHASE(2);
+    const uint32_t item = lds.items[slot], inst = (item & 0x7FFFFFFFu) >> 8, src = item & 255u;
+    WalkRay w;
+    w.o = V3(lds.ray[0 * 256 + src], lds.ray[1 * 256 + src], lds.ray[2 * 256 + src]);
+    w.d = V3(lds.ray[3 * 256 + src], lds.ray[4 * 256 + src], lds.ray[5 * 256 + src]);
+    w.near_ = lds.ray[6 * 256 + src], w.far_ = lds.ray[7 * 256 + src];
+    const InstanceXform x = load_instance_xform(s, inst);
+    WalkRay lr;
+    const float len = to_local<RCP>(x, w, lr, scene_fast);
+    if (item & RZ_BIN_WIDE) {
+        // the mesh is one leaf: its box once per visit (counted by lane 0 of the octet), then this lane's share of its triangles —
+        // each against the range the visit started with, shortened by this lane's own earlier hits; the octet's minimum below is
+        // what the one-by-one loop ends with (the nearest hit, the first in leaf order among equal distances)
+        const uint32_t j = slot & 7u;
+        const float4 n0 = s.nodes[2 * x.blas_root], n1 = s.nodes[2 * x.blas_root + 1];
+        RZ_PHASE(3);
+        if (j == 0u) { RZ_COUNT(box_tests); }
+        uint32_t wide_t = 0xFFFFFFFFu, wide_tri = 0xFFFFFFFFu;  // this lane's best triangle of the shared visit
+        float wide_b1 = 0.0f, wide_b2 = 0.0f;
+        bool wide_external = false;
+        const float visit_near = lr.near_;
+        if (box_hit_unpacked<RCP>(n0, n1, lr)) {
+            const uint32_t begin = __float_as_uint(n1.z), end = begin + (__float_as_uint(n1.w) & HIPRZ_NODE_COUNT_MASK);
+            for (uint32_t i = begin + j; i < end; i += 8u) {
+                const float4 a = s.tris[3 * i], b = s.tris[3 * i + 1], cc = s.tris[3 * i + 2];
+                float t, b1, b2, det;
+                RZ_PHASE(4);
+                RZ_COUNT(tri_tests);
+                if (tri_hit(xyz(a), xyz(b), xyz(cc), lr, t, b1, b2, det)) {
+                    lr.far_ = t;
+                    wide_t = __float_as_uint(t), wide_tri = i, wide_b1 = b1, wide_b2 = b2, wide_external = det > 0.0f;
+                }
+            }
+        }
+        // the octet's winner hands the visit's hit to the ray's slot (the 8 lanes of a visit take this branch together; distances
+        // are positive: their bits order like they do)
+        const uint32_t t_min = octet_min(wide_t);
+        const bool nearest = wide_t != 0xFFFFFFFFu && wide_t == t_min;
+        const uint32_t first = octet_min(nearest ? wide_tri : 0xFFFFFFFFu);
+        if (nearest && wide_tri == first) {
+            lds.ray[6 * 256 + src] = visit_near / len;
+            lds.ray[7 * 256 + src] = __uint_as_float(wide_t) / len;
+            lds.hit[0 * 256 + src] = wide_tri;
+            lds.hit[1 * 256 + src] = wide_external ? 1u : 0u;
+            lds.hit[2 * 256 + src] = __float_as_uint(wide_b1);
+            lds.hit[3 * 256 + src] = __float_as_uint(wide_b2);
+            lds.hit[4 * 256 + src] = inst;
+        }
+    } else {
+        LdsStack mesh(mesh_column);
+        Hit h;
+        if (closest_in_mesh_stack<COUNT, RCP, false>(s, mesh, x.blas_root, lr, h, cnt)) {  // single-leaf meshes: one box test per visit
+            lds.ray[6 * 256 + src] = lr.near_ / len;
+            lds.ray[7 * 256 + src] = lr.far_ / len;
+            lds.hit[0 * 256 + src] = h.triangle;
+            lds.hit[1 * 256 + src] = h.external ? 1u : 0u;
+            lds.hit[2 * 256 + src] = __float_as_uint(h.bx);
+            lds.hit[3 * 256 + src] = __float_as_uint(h.by);
+            lds.hit[4 * 256 + src] = inst;
+        }
+    }
+}
+
 // Must be called by ALL 256 threads of the workgroup (it contains barriers); `active` = this lane
 // carries a ray.  Returns 0 / 1 / 2 like closest_hit().
-template <bool COUNT, bool RCP, bool FLAT = false>  // FLAT: the host guarantees a one-leaf world tree (<= 8 instances)
+template <bool COUNT, bool RCP>
 __device__ __forceinline__ int closest_hit_binned(const DScene& s, unsigned char* workspace, bool active, Ray& ray, Hit& hit,
                                                   Counters& cnt) {
     const uint32_t tid = threadIdx.x;
@@ -797,20 +904,6 @@ __device__ __forceinline__ int closest_hit_binned(const DScene& s, unsigned char
     uint32_t leaf_i = 0, leaf_end = 0;
     bool root_missed = false;
     uint32_t round = 0u;
-    // a world of one leaf: its instance boxes are tested up front (pretest_leaf_instances)
-    const float4 root1 = s.nodes[2 * s.tlas_root + 1];
-    const uint32_t flat_begin = __float_as_uint(root1.z), flat_count = __float_as_uint(root1.w) & HIPRZ_NODE_COUNT_MASK;
-    const bool flat_world = FLAT;  // compile-time: the general world walk below drops out of the FLAT instantiation
-    float tm[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    uint32_t flat_mask = 0u, flat_next = 0u;
-    float flat_near = g.near_;
-    if (flat_world && active) {
-        const float4 root0 = s.nodes[2 * s.tlas_root];
-        RZ_PHASE(0);
-        RZ_COUNT(box_tests);
-        if (box_hit_unpacked<RCP>(root0, root1, g)) flat_mask = pretest_leaf_instances<COUNT, RCP>(s, flat_begin, flat_count, 0u, g, tm, true, cnt);
-        else root_missed = true;
-    }
     if (tid < 128u) lds.bins[tid] = 0u;
     // Visits of a mesh that is ONE leaf of more than 4 triangles (a Cornell cube: 12) are shared by 8 lanes: a wave's dense items are a
     // mix of such visits and of 2-triangle walls, and with one lane per visit the wave's triangle loop ran as long as its longest item
@@ -833,29 +926,6 @@ __device__ __forceinline__ int closest_hit_binned(const DScene& s, unsigned char
         // A. advance this ray to its next candidate instance (traverseWorld, cpu_engine_kernel.cpp:254-277, 305)
         RZ_PHASE(5);
         uint32_t cand = RZ_BIN_NONE;
-        if (flat_world) {
-            if (__any(flat_mask != 0u && __float_as_uint(g.near_) != __float_as_uint(flat_near))) {
-                // rare: a hit moved the near end by a rounding — the boxes not yet visited are tested again with it (the ray comes
-                // back from its LDS slot; the tests were counted the first time)
-                if (flat_mask != 0u && __float_as_uint(g.near_) != __float_as_uint(flat_near)) {
-                    WalkRay t;
-                    t.o = V3(lds.ray[0 * 256 + tid], lds.ray[1 * 256 + tid], lds.ray[2 * 256 + tid]);
-                    t.d = V3(lds.ray[3 * 256 + tid], lds.ray[4 * 256 + tid], lds.ray[5 * 256 + tid]);
-                    t.near_ = g.near_, t.far_ = g.far_;
-                    prepare<RCP>(t, scene_fast);
-                    flat_mask = pretest_leaf_instances<COUNT, RCP>(s, flat_begin, flat_count, flat_next, t, tm, false, cnt);
-                    flat_near = g.near_;
-                }
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; ++k) {
-                if (cand == RZ_BIN_NONE && k >= flat_next && ((flat_mask >> k) & 1u)) {
-                    flat_next = k + 1u;
-                    if (!(tm[k] > g.far_)) cand = s.tlas_order[flat_begin + k];
-                }
-            }
-            if (cand == RZ_BIN_NONE) flat_mask = 0u;
-        } else
         while (true) {
             RZ_GUARD(guard);
             if (leaf_i < leaf_end) {
@@ -996,6 +1066,133 @@ __device__ __forceinline__ int closest_hit_binned(const DScene& s, unsigned char
                     lds.hit[4 * 256 + src] = inst;
                 }
             }
+        }
+        __syncthreads();
+        round += 1u;
+        // D. the ray's owner picks up its (possibly shortened) range
+        g.near_ = lds.ray[6 * 256 + tid];
+        g.far_ = lds.ray[7 * 256 + tid];
+    }
+    // origin and direction were not kept in registers across the rounds: take them back from the slot
+    ray.o = V3(lds.ray[0 * 256 + tid], lds.ray[1 * 256 + tid], lds.ray[2 * 256 + tid]);
+    ray.d = V3(lds.ray[3 * 256 + tid], lds.ray[4 * 256 + tid], lds.ray[5 * 256 + tid]);
+    ray.near_ = g.near_, ray.far_ = g.far_;
+    const uint32_t inst = lds.hit[4 * 256 + tid];
+    if (inst != 0xFFFFFFFFu) {
+        hit.instance = int32_t(inst);
+        hit.triangle = lds.hit[0 * 256 + tid];
+        hit.external = lds.hit[1 * 256 + tid] != 0u;
+        hit.bx = __uint_as_float(lds.hit[2 * 256 + tid]);
+        hit.by = __uint_as_float(lds.hit[3 * 256 + tid]);
+    }
+    if (root_missed) return 0;
+    return hit.instance >= 0 ? 2 : 1;
+}
+
+
+// ---- MODE 4: the binned walk on a world of ONE leaf (at most 8 instances) ----
+// closest_hit_binned without a world tree to walk: the instance boxes are tested up front (pretest_leaf_instances), a round's pick of
+// the next candidate is a handful of integer operations (flat_pick: no LDS read, no dependent chain), the scan runs over the 8 bins
+// there can be, in registers (DPP row shifts), and the round that finds no visit leaves before the scan.  Rounds, visiting order,
+// arithmetic and work counters are those of closest_hit_binned on the same world.
+struct DppShr {  // flat_prefix8's lane shift: v of the lane N below within the row of 16, 0 where there is none (row_shr:N, bound_ctrl)
+    template <int N>
+    __device__ __forceinline__ uint32_t operator()(uint32_t v, FlatShift<N>) const {
+        return uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x110 + N, 0xF, 0xF, true));
+    }
+};
+// Must be called by ALL 256 threads of the workgroup (it contains barriers); `active` = this lane carries a ray.  Returns 0 / 1 / 2
+// like closest_hit().
+template <bool COUNT, bool RCP>
+__device__ __forceinline__ int closest_hit_flat(const DScene& s, const FlatWorld& fw, unsigned char* workspace, bool active, Ray& ray, Hit& hit,
+                                                Counters& cnt) {
+    const uint32_t tid = threadIdx.x;
+    BinnedLds lds(workspace);
+    hit.instance = -1, hit.triangle = 0, hit.bx = hit.by = 0.0f, hit.external = true;
+    if (s.n_instances == 0) return 0;  // uniform
+
+    lds.ray[0 * 256 + tid] = ray.o.x, lds.ray[1 * 256 + tid] = ray.o.y, lds.ray[2 * 256 + tid] = ray.o.z;
+    lds.ray[3 * 256 + tid] = ray.d.x, lds.ray[4 * 256 + tid] = ray.d.y, lds.ray[5 * 256 + tid] = ray.d.z;
+    lds.ray[6 * 256 + tid] = ray.near_, lds.ray[7 * 256 + tid] = ray.far_;
+    lds.hit[4 * 256 + tid] = 0xFFFFFFFFu;
+
+    uint32_t* mesh_column = lds.stacks + s.world_stack_entries * 256u + tid;
+    WalkRay g;
+    g.o = ray.o, g.d = ray.d, g.near_ = ray.near_, g.far_ = ray.far_;
+    const bool scene_fast = s.fast_div != 0u;
+    prepare<RCP>(g, scene_fast);
+    bool root_missed = false;
+    uint32_t round = 0u;
+    float tm[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t flat_mask = 0u, flat_next = 0u;
+    float flat_near = g.near_;
+    if (active) {
+        RZ_PHASE(0);
+        RZ_COUNT(box_tests);
+        if (box_hit_unpacked<RCP>(fw.root0, fw.root1, g)) flat_mask = pretest_leaf_instances<COUNT, RCP>(s, fw, g, tm, true, cnt);
+        else root_missed = true;
+    }
+    // both halves of the double-buffered bins: the round that left the previous call found its own half empty and left the other one,
+    // the counts of the round before it, as they were
+    if (tid < 128u) lds.bins[tid] = 0u;
+    __syncthreads();
+
+    const uint32_t lane = tid & 63u;
+    const bool wide_bin = ((fw.wide >> (lane & 7u)) & 1u) != 0u;
+    while (round < (1u << 20)) {  // workgroup-uniform bound: a ray enters each instance at most once
+        // A. this ray's next candidate instance (traverseWorld, cpu_engine_kernel.cpp:254-277, 305)
+        RZ_PHASE(5);
+        if (__any(flat_mask != 0u && __float_as_uint(g.near_) != __float_as_uint(flat_near))) {
+            // rare: a hit moved the near end by a rounding — the boxes not yet visited are tested again with it (the ray comes
+            // back from its LDS slot; the tests were counted the first time)
+            if (flat_mask != 0u && __float_as_uint(g.near_) != __float_as_uint(flat_near)) {
+                WalkRay t;
+                t.o = V3(lds.ray[0 * 256 + tid], lds.ray[1 * 256 + tid], lds.ray[2 * 256 + tid]);
+                t.d = V3(lds.ray[3 * 256 + tid], lds.ray[4 * 256 + tid], lds.ray[5 * 256 + tid]);
+                t.near_ = g.near_, t.far_ = g.far_;
+                prepare<RCP>(t, scene_fast);
+                flat_mask = pretest_leaf_instances<COUNT, RCP>(s, fw, t, tm, false, cnt) & flat_from(flat_next);
+                flat_near = g.near_;
+            }
+        }
+        const uint32_t cand = flat_pick(fw.ids, tm, g.far_, flat_mask, flat_next);
+
+        // B. bin the items by instance: count (LDS atomics), exclusive prefix over the 8 bins computed redundantly by every wave (no
+        //    barrier between scan and scatter), scatter.  The bins are double-buffered: this round's were zeroed during the previous round.
+        uint32_t* bins = lds.bins + (round & 1u) * 64u;
+        uint32_t rank = 0u;
+        const bool wide_item = cand != kFlatNone && ((fw.wide >> cand) & 1u) != 0u;
+        if (cand != kFlatNone) rank = atomicAdd(&bins[cand], wide_item ? 8u : 1u);  // in lanes: 8 per visit of a wide instance
+        __syncthreads();
+        const uint32_t c = bins[lane];  // (bins 8..63 stay zero: an instance id is below 8)
+        // No visit in the whole workgroup: the walk is over.  WORKGROUP-UNIFORM, as an exit ahead of the barriers below must be: every
+        // wave reads the same words here, behind the same barrier, and nothing writes this half of the bins before the next one (the
+        // zeroing below and the next round's atomics go to the other half).
+        if (!__any(c != 0u)) break;
+        const uint32_t own = flat_pack_bin(c, wide_bin);
+        const uint32_t incl = flat_prefix8(own, DppShr{});  // lanes 0..7 of every row of 16; lanes 8..15 are not looked at
+        const FlatRound r = flat_round(uint32_t(__builtin_amdgcn_readlane(int(incl), 7)));
+#ifdef RZ_PHASE_STATS
+        if (!r.split) { RZ_PHASE(6); }  // rounds on the one-lane-per-visit fallback
+#endif
+        const uint32_t before = __shfl(incl - own, int(cand & 7u));
+        if (cand != kFlatNone) {
+            const uint32_t at = flat_item_slot(r, before, rank, wide_item);
+            if (r.split && wide_item) {
+#pragma unroll
+                for (uint32_t j = 0; j < 8u; ++j) lds.items[at + j] = RZ_BIN_WIDE | (cand << 8) | tid;
+            } else {
+                lds.items[at] = (cand << 8) | tid;
+            }
+        }
+        if (tid < 64u) lds.bins[((round + 1u) & 1u) * 64u + tid] = 0u;
+        __syncthreads();
+
+        // C. dense: one lane per item — eight per visit of a wide instance (binned_visit).  The lane that takes item i rotates with the
+        //    round and the workgroup, so the busy waves — and with them the SIMDs they live on — change from round to round.
+        const uint32_t slot = (tid - ((blockIdx.x + round) & 3u) * 64u) & 255u;
+        if (slot < r.n_items) {
+            binned_visit<COUNT, RCP>(s, lds, mesh_column, scene_fast, slot, cnt);
         }
         __syncthreads();
         round += 1u;

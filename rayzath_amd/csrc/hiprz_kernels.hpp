@@ -97,13 +97,23 @@ RZ_DEV void load_path(const DFrame& f, const DCamera& cam, const PixelId& p, Pat
 }
 
 // closest hit of the segment with the selected walk; MODE 2 must be reached by all 256 threads
-// MODE 4 = MODE 2 for a world tree of ONE leaf with at most 8 instances (the host checks it at upload): the instantiation without the
-// general world walk, whose state would only cost registers (closest_hit_binned<..., FLAT>)
+// MODE 4 = MODE 2 for a world tree of ONE leaf with at most 8 instances (the host checks it at upload): a walk of its own without the
+// general world walk (closest_hit_flat)
 constexpr bool binned_mode(int mode) { return mode == 2 || mode == 4; }
-template <int MODE, bool COUNT, bool RCP>
-RZ_DEV int trace_path(const DScene& s, unsigned char* workspace, uint32_t* lds_column, bool active, Ray& ray, Hit& hit, Counters& cnt) {
-    if constexpr (binned_mode(MODE)) {
-        return closest_hit_binned<COUNT, RCP, MODE == 4>(s, workspace, active, ray, hit, cnt);
+// What a walk derives from the scene alone, built once per launch or tile and handed to every trace_path of it (whole waves must reach
+// walk_world): MODE 4's FlatWorld, nothing for the other walks.
+struct NoWorld {};
+template <int MODE>
+RZ_DEV auto walk_world(const DScene& s) {
+    if constexpr (MODE == 4) return make_flat_world(s);
+    else return NoWorld{};
+}
+template <int MODE, bool COUNT, bool RCP, class WORLD>
+RZ_DEV int trace_path(const DScene& s, const WORLD& world, unsigned char* workspace, uint32_t* lds_column, bool active, Ray& ray, Hit& hit, Counters& cnt) {
+    if constexpr (MODE == 4) {
+        return closest_hit_flat<COUNT, RCP>(s, world, workspace, active, ray, hit, cnt);
+    } else if constexpr (MODE == 2) {
+        return closest_hit_binned<COUNT, RCP>(s, workspace, active, ray, hit, cnt);
     } else {
         hit.instance = -1, hit.triangle = 0, hit.bx = hit.by = 0.0f, hit.external = true;
         return active ? closest_hit<MODE, COUNT, RCP>(s, lds_column, ray, hit, cnt) : 0;
@@ -322,19 +332,20 @@ __global__ void __launch_bounds__(256, RZ_MIN_WAVES) rz_pass_kernel(const DScene
     load_path<FIRST>(f, cam, p, ps);
     Hit hit;
     int found;
+    const auto world = walk_world<MODE>(s);
     if constexpr (binned_mode(MODE)) {  // what the walk does not read is parked in LDS meanwhile
         // 4 KiB behind the binned walk's workspace (the launch plan adds them to the fused kernel's LDS size)
         static_assert(kFusedParkBytes == 4u * 256u * sizeof(uint32_t), "park [4][256]");
         uint32_t* park = reinterpret_cast<uint32_t*>(workspace + BinnedLds::kFixedBytes + (s.world_stack_entries + s.mesh_stack_entries) * 1024u);
         park[0 * 256 + threadIdx.x] = __float_as_uint(ps.color.r), park[1 * 256 + threadIdx.x] = __float_as_uint(ps.color.g);
         park[2 * 256 + threadIdx.x] = __float_as_uint(ps.color.b), park[3 * 256 + threadIdx.x] = ps.material | (ps.depth << 16);
-        found = trace_path<MODE, COUNT, RZ_FUSED_SHARED_RCP != 0>(s, workspace, lds_column, p.active, ps.ray, hit, cnt);
+        found = trace_path<MODE, COUNT, RZ_FUSED_SHARED_RCP != 0>(s, world, workspace, lds_column, p.active, ps.ray, hit, cnt);
         ps.color = col4{__uint_as_float(park[0 * 256 + threadIdx.x]), __uint_as_float(park[1 * 256 + threadIdx.x]),
                         __uint_as_float(park[2 * 256 + threadIdx.x]), 1.0f};
         const uint32_t bits = park[3 * 256 + threadIdx.x];
         ps.material = bits & 0xFFFFu, ps.depth = bits >> 16;
     } else {
-        found = trace_path<MODE, COUNT, RZ_FUSED_SHARED_RCP != 0>(s, workspace, lds_column, p.active, ps.ray, hit, cnt);
+        found = trace_path<MODE, COUNT, RZ_FUSED_SHARED_RCP != 0>(s, world, workspace, lds_column, p.active, ps.ray, hit, cnt);
     }
     if (p.active) shade_and_store<FIRST, COUNT>(s, cam, cfg, f, p, ps, found, hit, ShadowCtx{lds_column, TopCache{nullptr, nullptr, 0u}}, cnt);
     flush_counters<COUNT>(f, p.active ? 1u : 0u, cnt);
@@ -365,6 +376,7 @@ RZ_DEV void batch_tile(const DScene& s, const DCamera& cam, const DConfig& cfg, 
         park[4 * 256] = __float_as_uint(acc.x), park[5 * 256] = __float_as_uint(acc.y);
         park[6 * 256] = __float_as_uint(acc.z), park[7 * 256] = __float_as_uint(acc.w);
     }
+    const auto world = walk_world<MODE>(s);  // once per tile: the passes walk the same scene
     for (uint32_t i = 0; i < n_passes; ++i) {
         if (i != 0u && p.active) {  // what load_path does with the state the previous pass stored
             ps.ray.d = normalized(ps.ray.d);
@@ -376,12 +388,12 @@ RZ_DEV void batch_tile(const DScene& s, const DCamera& cam, const DConfig& cfg, 
         if constexpr (binned_mode(MODE)) {
             park[0 * 256] = __float_as_uint(ps.color.r), park[1 * 256] = __float_as_uint(ps.color.g);
             park[2 * 256] = __float_as_uint(ps.color.b), park[3 * 256] = ps.material | (ps.depth << 16);
-            found = trace_path<MODE, COUNT, RZ_BATCH_SHARED_RCP != 0>(s, workspace, lds_column, p.active, ps.ray, hit, cnt);
+            found = trace_path<MODE, COUNT, RZ_BATCH_SHARED_RCP != 0>(s, world, workspace, lds_column, p.active, ps.ray, hit, cnt);
             ps.color = col4{__uint_as_float(park[0 * 256]), __uint_as_float(park[1 * 256]), __uint_as_float(park[2 * 256]), 1.0f};
             const uint32_t bits = park[3 * 256];
             ps.material = bits & 0xFFFFu, ps.depth = bits >> 16;
         } else {
-            found = trace_path<MODE, COUNT, RZ_BATCH_SHARED_RCP != 0>(s, workspace, lds_column, p.active, ps.ray, hit, cnt);
+            found = trace_path<MODE, COUNT, RZ_BATCH_SHARED_RCP != 0>(s, world, workspace, lds_column, p.active, ps.ray, hit, cnt);
         }
         if (p.active) {
             col4 final_color;
@@ -566,7 +578,7 @@ __global__ void __launch_bounds__(256, RZ_TRACE_MIN_WAVES) rz_trace_kernel(const
         ray = ps.ray;
     }
     Hit hit;
-    const int found = trace_path<MODE, COUNT, RZ_TRACE_SHARED_RCP != 0>(s, workspace, lds_column, p.active, ray, hit, cnt);
+    const int found = trace_path<MODE, COUNT, RZ_TRACE_SHARED_RCP != 0>(s, walk_world<MODE>(s), workspace, lds_column, p.active, ray, hit, cnt);
     if (p.active) {
         f.hit0[p.local] = make_float4(ray.far_, hit.bx, hit.by, __uint_as_float(hit.triangle));
         f.hit1[p.local] = (uint32_t(hit.instance) & 0x1FFFFFFFu) | (uint32_t(found) << 29) | (hit.external ? 0x80000000u : 0u);

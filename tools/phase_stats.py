@@ -6,7 +6,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rayzath_amd import scenes
 from rayzath_amd.engine import Context, RenderConfig, Tracing
 from rayzath_amd.scene import camera_struct, flatten
-NAMES = ["world node box test", "instance box test", "instance entry (to local)", "mesh node box test", "triangle test", "mesh walk round"]
+NAMES = ["world node box test", "instance box test", "instance entry (to local)", "mesh node box test", "triangle test", "mesh walk round",
+         "round on one lane per visit"]   # (the one-leaf binned walk: a round whose octets would not fit the workgroup)
 for cfgname in sys.argv[1:] or ["D"]:
     preset = scenes.CONFIGS[cfgname]
     w = preset["build"]()
