@@ -434,6 +434,12 @@ int hiprz_set_lds_scene(hiprz_ctx* ctx, int mode);
  * walk), else 1.  Identical results. */
 int hiprz_set_pipeline(hiprz_ctx* ctx, int pipeline);
 int hiprz_pipeline(hiprz_ctx* ctx, int* effective_pipeline_out); /* valid after hiprz_upload_scene */
+/* The launch plan of the most recent render call of this context (on a context over several devices or streams: of its head part) as
+ * 32-bit words: which kernel instantiation every launch of that call selected, with which grid and how much LDS.  The words are the
+ * members of the library's LaunchPlan record in order (tests/test_launch_plan.py: PLAN_FIELDS); the layout belongs to this build of the
+ * library and is no part of the stable interface.  Read-only: launches nothing, changes nothing.  HIPRZ_ERR_INVALID on a null argument
+ * or when `capacity` (in words) is too small, HIPRZ_ERR_STATE before the first render call. */
+int hiprz_launch_plan(hiprz_ctx* ctx, uint32_t* words, uint32_t capacity, uint32_t* n_words_out);
 /* Reorder rays between passes (split pipeline): the shade kernel emits a sort key per pixel (cell of the next
  * ray's origin interleaved with the cell where that ray leaves the world box), a device radix sort turns the keys into a permutation, and the trace kernel
  * walks the rays in that order so that a wave's rays visit the same nodes.  -1 = automatic (on for scenes that are

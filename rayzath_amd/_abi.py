@@ -156,6 +156,7 @@ ENTRY_POINTS = {
     "hiprz_set_pipeline": (C.c_int, [P, C.c_int]),
     "hiprz_traversal_mode": (C.c_int, [P, C.POINTER(C.c_int)]),
     "hiprz_pipeline": (C.c_int, [P, C.POINTER(C.c_int)]),
+    "hiprz_launch_plan": (C.c_int, [P, C.POINTER(U32), U32, C.POINTER(U32)]),
     "hiprz_set_ray_sort": (C.c_int, [P, C.c_int]),
     "hiprz_set_xcd_swizzle": (C.c_int, [P, C.c_int]),
     "hiprz_set_graph": (C.c_int, [P, C.c_int]),

@@ -470,6 +470,7 @@ int render_passes(hiprz_ctx* c, uint32_t n_passes, bool counted) {
     resolve_pipeline(c);  // the choice depends on the selected camera's shard size too
     StageTimer timer;
     c->plan = plan_launches(plan_inputs(c), counted);
+    c->have_plan = true;
     if (c->plan.defer_shadows) {  // hand-over buffers of the deferred shadow rays: (4 + 2 * samples) float4 per owned pixel
         const size_t n = size_t(c->n_local_tiles) * 256u * c->plan.nee_quads;
         if (c->nee.count < n) c->graph_valid = false;
@@ -976,6 +977,17 @@ int hiprz_pipeline(hiprz_ctx* c, int* out) {
 int hiprz_traversal_mode(hiprz_ctx* c, int* out) {
     if (!c || !out) return HIPRZ_ERR_INVALID;
     *out = int(plan_launches(plan_inputs(c), false).reported_mode);
+    return HIPRZ_OK;
+}
+
+int hiprz_launch_plan(hiprz_ctx* c, uint32_t* words, uint32_t capacity, uint32_t* n_words_out) {
+    constexpr uint32_t n = uint32_t(sizeof(LaunchPlan) / sizeof(uint32_t));
+    static_assert(sizeof(LaunchPlan) == n * sizeof(uint32_t), "LaunchPlan is 32-bit words without padding");
+    if (!c || !words || !n_words_out) return HIPRZ_ERR_INVALID;
+    if (capacity < n) return fail(c, HIPRZ_ERR_INVALID, "launch_plan: the buffer holds fewer than " + std::to_string(n) + " words");
+    if (!c->have_plan) return fail(c, HIPRZ_ERR_STATE, "launch_plan: no render call has planned its launches yet");
+    std::memcpy(words, &c->plan, sizeof(LaunchPlan));
+    *n_words_out = n;
     return HIPRZ_OK;
 }
 

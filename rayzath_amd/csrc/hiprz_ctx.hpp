@@ -248,6 +248,7 @@ struct hiprz_ctx : hiprz_frame_state {
     int pipeline_setting = -1;  // hiprz_set_pipeline: -1 = per scene (hiprz_plan.cpp: choose_pipeline)
     int pipeline = 1;  // resolved by resolve_pipeline() at upload / set time and before a render call
     hiprz::LaunchPlan plan{};  // of the render call being enqueued (render_passes): what every launch of it selects
+    bool have_plan = false;    // a render call has computed `plan` (hiprz_launch_plan)
     uint32_t wave_resident_max = 1u << 30;  // HIPRZ_WAVE_RESIDENT_MAX (hiprz_plan.cpp: choose_pipeline)
     // device-built trees (hiprz_set_tree(HIPRZ_TREE_DEVICE), hiprz_build.hip): the 32-byte node records of the whole scene in a buffer of
     // their own (the hot blob's node section only holds the uploaded prefix), the workspaces of build and refit, the meshes

@@ -226,6 +226,12 @@ class Context:
         self._check(self.lib.hiprz_pipeline(self._ctx, C.byref(v)))
         return v.value
 
+    def launch_plan(self):
+        """The launch plan of the most recent render call (hiprz_launch_plan) as its raw uint32 words."""
+        words, n = np.zeros(256, dtype=np.uint32), C.c_uint32()
+        self._check(self.lib.hiprz_launch_plan(self._ctx, words.ctypes.data_as(C.POINTER(C.c_uint32)), len(words), C.byref(n)))
+        return words[:n.value].copy()
+
     def graph_captures(self):
         v = C.c_uint32()
         self._check(self.lib.hiprz_graph_captures(self._ctx, C.byref(v)))

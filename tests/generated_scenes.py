@@ -245,13 +245,34 @@ FEATURES = {
     "max_depth 16": lambda w, c: c.tracing.max_depth == 16,
 }
 
+# Scenes derived from sweep scenes, addressed as (kind, seed) wherever a seed is: "dark" is scene `seed` without its lights, "bare" without
+# lights and without any map.  No scene of SEEDS is both (the six without lights all carry a map), and the library has instantiations
+# for exactly these: shading without next-event estimation (RZ_SHADOW_NONE) and without texture fetches as well (RZ_SHADOW_PLAIN).
+# tests/test_packaging_sweep_gpu.py needs them on one-leaf worlds (1, 3, 5, 9), on deeper world trees (0, 2, 8, 10) and on the empty
+# world (7) to reach every kernel instantiation; tests/test_lockstep_gpu.py holds the default packaging on them to the oracle.
+DERIVED = tuple(("bare", s) for s in (0, 1, 2, 3, 5, 7, 8, 9)) + tuple(("dark", s) for s in (0, 2, 10))
+_MAPS = ("texture", "normal_map", "metalness_map", "roughness_map", "emission_map")
+
+
+def derived_world(kind, seed):
+    """(World, RenderConfig) of the derived scene (kind, seed)"""
+    assert kind in ("dark", "bare"), kind
+    world, config = generated_world(seed)
+    world.spot_lights.clear(), world.direct_lights.clear()
+    if kind == "bare":
+        for m in [world.material] + list(world.materials):
+            for field in _MAPS:
+                setattr(m, field, None)
+    return world, config
+
+
 _CACHE = {}
 
 
 def flat_scene(seed):
-    """(FlatScene, hiprz_camera, hiprz_config, World, RenderConfig) of sweep scene `seed`, built once."""
+    """(FlatScene, hiprz_camera, hiprz_config, World, RenderConfig) of sweep scene `seed` (or of the derived scene (kind, seed)), built once."""
     if seed not in _CACHE:
         from rayzath_amd.scene import camera_struct, flatten
-        world, config = generated_world(seed)
+        world, config = derived_world(*seed) if isinstance(seed, tuple) else generated_world(seed)
         _CACHE[seed] = (flatten(world), camera_struct(world.camera), config.struct(), world, config)
     return _CACHE[seed]

@@ -29,13 +29,23 @@ CONTINUOUS = ("origin", "direction", "color")
 
 
 class OracleDevice:
-    """An OracleRenderer in the device's place: render(1), read_accum(), read_state(), read_depth() (and render_counted)."""
+    """An OracleRenderer in the device's place: render(n), read_accum(), read_state(), read_depth() (and render_counted); reset(),
+    ray_count() and pass_count() for tests/packaging_sweep.py."""
 
     def __init__(self, renderer, threads=1):
         self.renderer, self.threads = renderer, threads
 
     def render(self, n):
         self.renderer.render(n, threads=self.threads)
+
+    def reset(self):
+        self.renderer.reset()
+
+    def ray_count(self):
+        return self.renderer.traced_rays
+
+    def pass_count(self):
+        return self.renderer.passes
 
     def render_counted(self, n):
         return self.renderer.render(n, threads=self.threads, counted=True)

@@ -57,6 +57,15 @@ def test_create_fails_loudly_without_a_gpu(built):
     assert b"HIP device" in lib.hiprz_last_error(None)
 
 
+def test_launch_plan_refuses_null_arguments(built):
+    """hiprz_launch_plan without a context (none can exist without a GPU): refused, and nothing is written"""
+    lib = _lib.load()
+    words, n = (C.c_uint32 * 64)(*([0xABCD] * 64)), C.c_uint32(77)
+    assert lib.hiprz_launch_plan(None, words, 64, C.byref(n)) == _abi.ERR_INVALID
+    assert lib.hiprz_launch_plan(None, None, 0, None) == _abi.ERR_INVALID
+    assert n.value == 77 and set(words) == {0xABCD}
+
+
 def test_every_launch_site_registered_its_kernel_and_the_built_files_hold_them(built):
     """hiprz_kernel_count(): the kernel instantiations the launchers can select, registered when the library was loaded (RZ_LAUNCH); the first
     hiprz_create on a device resolves each of them in the loaded code objects.  tools/check_kernels.py proves on the built files — no GPU

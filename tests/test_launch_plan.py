@@ -10,6 +10,9 @@ built with a sanitizer is loaded into this process).
    asserts that coverage, and that every enumerator of every variant record is produced.
 2. Invariants that do not depend on the restatement.
 3. libhiprz.so holds exactly the kernels the library of a709859 held (tests/golden/launch_plan/kernels_a709859.txt).
+4. The kernel instantiations the uncounted plans of (1) name (kernel_identities) are the committed list
+   tests/golden/launch_plan/identities.txt — what tests/test_packaging_sweep_gpu.py has to reach on the device.  The list is written by
+   write_identities: run test_plan_against_the_parents_rules_and_invariants with HIPRZ_WRITE_IDENTITIES=1 after a rule changed on purpose.
 """
 import itertools
 import os
@@ -257,7 +260,54 @@ def check_invariants(r, p):
         implies((p[field] > 160 * KIB) & ~known, np.zeros(len(r), bool), f"{field} <= 160 KiB")
 
 
+# What names a kernel instantiation in a plan: per launch, the record that says whether the launch is made and the fields the launchers
+# dispatch on (hiprz_launch_*.hip) — grids, LDS sizes and tree-top counts are launch arguments, not instantiations.
+IDENTITY_FIELDS = {
+    "trace": ("trace.family", ["trace.family", "trace.waves", "trace.one_leaf", "trace.mode", "trace.lds_scene"]),
+    "shade": ("shade.active", ["shade.lds_scene", "shade.shadow"]),
+    "follow": ("shade.follow", ["shade.follow"]),
+    "fused": ("fused.family", ["fused.family", "fused.mode", "fused.lds_scene"]),
+    "batch": ("batch.family", ["batch.family", "batch.mode", "batch.lds_scene", "batch.shading", "batch.five", "batch.one_leaf", "batch.segment_cap"]),
+}
+IDENTITIES = os.path.join(ROOT, "tests", "golden", "launch_plan", "identities.txt")
+
+
+def kernel_identities(plan_record):
+    """The kernel instantiations the plan(s) launch, as a set of tuples: ("trace", family, waves, one_leaf, mode, lds_scene),
+    ("shade", lds_scene, shadow), ("follow", follow), ("fused", family, mode, lds_scene),
+    ("batch", family, mode, lds_scene, shading, five, one_leaf, segment_cap > 1); a launch the plan does not make is left out.
+    `plan_record`: one record or an array of plan_dtype, or the raw uint32 words of Context.launch_plan()."""
+    p = np.atleast_1d(np.asarray(plan_record))
+    if p.dtype != plan_dtype:
+        p = np.ascontiguousarray(p, dtype=np.uint32).view(plan_dtype)
+    out = set()
+    for kind, (launched, fields) in IDENTITY_FIELDS.items():
+        rows = p[p[launched] != 0]
+        if not len(rows):
+            continue
+        columns = [(rows[f] > 1) if f == "batch.segment_cap" else rows[f] for f in fields]
+        for row in np.unique(np.stack(columns, axis=1).astype(np.int64), axis=0):
+            out.add((kind, *(int(v) for v in row)))
+    return out
+
+
+def identity_line(identity):
+    return " ".join(str(v) for v in identity)
+
+
+def read_identities():
+    """tests/golden/launch_plan/identities.txt: every identity an uncounted plan of the input space below holds, one per line, sorted"""
+    with open(IDENTITIES) as f:
+        return {(w[0], *(int(v) for v in w[1:])) for w in (line.split() for line in f) if w}
+
+
+def write_identities(identities):
+    with open(IDENTITIES, "w") as f:
+        f.write("".join(identity_line(i) + "\n" for i in sorted(identities)))
+
+
 def test_plan_against_the_parents_rules_and_invariants(program):
+    identities = set()
     seen_value = {a: np.zeros(len(VALUES[a]), bool) for a in AXES}
     seen_pair = {(a, b): np.zeros(len(VALUES[a]) * len(VALUES[b]), bool) for a in AXES for b in DRAWN if a != b}
     produced = {f: set() for f in PLAN_FIELDS if f.split(".")[-1] in ("family", "follow", "shadow", "shading", "mode", "waves", "pipeline", "reported_mode", "walk_mode")}
@@ -277,6 +327,8 @@ def test_plan_against_the_parents_rules_and_invariants(program):
                 bad = np.flatnonzero(p[field] != want[field])
                 assert bad.size == 0, f"{field} (counted {counted}): {bad.size} of {len(r)} differ, first: {r[bad[0]]} gives {p[field][bad[0]]}, the parent's rules {want[field][bad[0]]}"
             check_invariants(r, p)
+            if not counted:
+                identities |= kernel_identities(p)
             for field, values in produced.items():
                 values.update(np.unique(p[field]).tolist())
     assert total == int(np.prod([len(v) for v in CROSS.values()]))
@@ -290,6 +342,12 @@ def test_plan_against_the_parents_rules_and_invariants(program):
               "fused.family": {0, 1, 2}, "fused.mode": {0, 1, 2, 4},
               "batch.family": {0, 1, 2}, "batch.mode": {0, 1, 2, 3, 4}, "batch.shading": {0, 1, NONE, PLAIN}}
     assert produced == expect
+    # the instantiations the uncounted plans name: the universe tests/test_packaging_sweep_gpu.py has to reach (or exempt with a reason)
+    if os.environ.get("HIPRZ_WRITE_IDENTITIES"):
+        write_identities(identities)
+    want = read_identities()
+    assert identities == want, (f"not in identities.txt: {sorted(identities - want)[:5]}, no longer produced: {sorted(want - identities)[:5]} "
+                                "(HIPRZ_WRITE_IDENTITIES=1 writes the list again)")
 
 
 PINNED = dict(pipeline_setting=2, traversal_mode=-1, lds_scene_override=1, walk_order=1, sort_rays=-1, shadow_sort=1, shadow_packet=-1, defer_shadow_rays=1,

@@ -12,6 +12,8 @@ test_cuda_compat_oracle_gpu.py, and the only one).  ray_count() and pass_count()
 
 Run with -s for the per-configuration totals beside their caps; the measured figures are in DESIGN.md (Oracle, "Lockstep").
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -26,6 +28,7 @@ pytestmark = pytest.mark.gpu
 
 CHUNK = 10
 CHUNKS = [G.SEEDS[i:i + CHUNK] for i in range(0, len(G.SEEDS), CHUNK)]
+DERIVED_CHUNK = len(CHUNKS)   # run_chunk's index of generated_scenes.DERIVED, which is no part of the sweep's totals
 CONFIGS = {name: dict(settings=settings) for name, settings in PACKAGINGS.items()}
 CONFIGS["two-streams"] = dict(devices=[0, 0])
 CONFIGS["tree-device"] = dict(settings=dict(tree=TREE_DEVICE))
@@ -33,11 +36,22 @@ CONFIGS["tree-device-sah"] = dict(settings=dict(tree=TREE_DEVICE_SAH))
 for _mode in (31, 63):
     CONFIGS[f"compat{_mode}-fused"] = dict(mode=_mode, pipeline=0, settings=dict(mode=_mode, pipeline=0))
     CONFIGS[f"compat{_mode}-split"] = dict(mode=_mode, pipeline=1, settings=dict(mode=_mode))   # the default must resolve to the split pipeline
+# what tests/test_packaging_sweep_gpu.py found to render other last bits than "compat31-split" (coloured shadow masks are products in the
+# order a walk meets the crossed triangles; that file's VARIANTS say where): each order is held to the oracle here
+CONFIGS["compat31-inline-shadows"] = dict(mode=31, pipeline=1, settings=dict(mode=31), env={"HIPRZ_DEFER_SHADOWS": "0"})
+CONFIGS["compat31-shadow-beams"] = dict(mode=31, pipeline=1, settings=dict(mode=31), env={"HIPRZ_SHADOW_PACKET": "1"})
+CONFIGS["compat31-tree-device-sah"] = dict(mode=31, pipeline=1, settings=dict(mode=31, tree=TREE_DEVICE_SAH))
 _RESULTS = {}
 
 
 def _context(config):
-    ctx = Context(config.get("devices", 0))
+    saved = {k: os.environ.get(k) for k in config.get("env", {})}
+    os.environ.update(config.get("env", {}))   # read by hiprz_create
+    try:
+        ctx = Context(config.get("devices", 0))
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
     for k, v in config.get("settings", {}).items():
         getattr(ctx, "set_" + k)(v)
     return ctx
@@ -66,7 +80,7 @@ def run_chunk(name, chunk, counted=False):
     config, out = CONFIGS[name], {}
     mode = config.get("mode", 0)
     ctx = _context(config)
-    for seed in CHUNKS[chunk]:
+    for seed in (CHUNKS + [G.DERIVED])[chunk]:
         flat, cam, cfg = G.flat_scene(seed)[:3]
         if mode & COMPAT_REPROJECTION:
             # a context that keeps its frame size blends the previous scene's frame into pass 0 (hiprz_upload_camera drops the history on
@@ -126,6 +140,25 @@ def test_lockstep_sweep_total(built, name):
     print(f"lockstep sweep {name}: {total['segments']} segments, exact {total['exact']}, far {total['far']}, discrete {total['discrete']}, "
           f"cap on far + discrete {cap}")
     assert total["far"] + total["discrete"] <= cap, "\n".join(worst)
+
+
+@pytest.mark.parametrize("name", ["default", "compat31-split"])
+def test_lockstep_derived_scenes(built, name):
+    """The scenes without lights and without maps derived from sweep scenes (generated_scenes.DERIVED) under the per-scene rule above, in
+    the two configurations whose pass-by-pass renders are the baselines of tests/test_packaging_sweep_gpu.py: that file's bit-equalities
+    carry this comparison to every other packaging on these scenes too."""
+    mode = CONFIGS[name].get("mode", 0)
+    failures = []
+    for seed, r in run_chunk(name, DERIVED_CHUNK).items():
+        cap = lockstep.scene_cap(seed, mode)
+        print(f"lockstep {name} scene {seed}: {r['segments']} segments, exact {r['exact']}, far {r['far']}, discrete {r['discrete']}, cap {cap}")
+        _check_depth(r, seed, mode)
+        cam = G.flat_scene(seed)[1]
+        assert r["rays"][0] == r["rays"][1] == G.PASSES * cam.width * cam.height, (seed, r["rays"])
+        assert r["passes"][0] == r["passes"][1] == G.PASSES, (seed, r["passes"])
+        if bad(r) > cap:
+            failures.append(f"scene {seed}: {r['discrete']} discrete + {r['far']} far segments, cap {cap}\n{lockstep.describe(r)}")
+    assert not failures, "\n".join(failures)
 
 
 @pytest.mark.parametrize("name", list(PACKAGINGS))

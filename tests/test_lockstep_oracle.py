@@ -49,6 +49,24 @@ def test_sweep_has_sixty_scenes_that_the_validator_accepts(built):
         assert lib.hiprz_validate_scene(C.byref(G.flat_scene(seed)[0].struct), msg, 256) == 0, (seed, msg.value.decode())
 
 
+def test_derived_scenes_have_no_lights_and_no_maps(built):
+    """generated_scenes.DERIVED: "dark" scenes keep their maps and lose their lights, "bare" scenes lose both; the validator accepts them,
+    the oracle's frames stay finite, and they are what SEEDS lacks: a scene without lights that has no map either"""
+    from rayzath_amd import _lib
+    lib = _lib.load()
+    assert not [s for s in G.SEEDS if not len(G.flat_scene(s)[0].textures) and not len(G.flat_scene(s)[0].spot_lights) + len(G.flat_scene(s)[0].direct_lights)]
+    for key in G.DERIVED:
+        flat, original = G.flat_scene(key)[0], G.flat_scene(key[1])[0]
+        msg = C.create_string_buffer(256)
+        assert lib.hiprz_validate_scene(C.byref(flat.struct), msg, 256) == 0, (key, msg.value.decode())
+        assert len(flat.spot_lights) == len(flat.direct_lights) == 0 and len(flat.instances) == len(original.instances), key
+        assert (len(flat.textures) == 0) if key[0] == "bare" else (len(flat.textures) == len(original.textures) > 0), key
+        ref = _renderer(key)
+        ref.render(G.PASSES, threads=1)
+        assert np.isfinite(ref.accum).all() and all(np.isfinite(v).all() for v in ref.state.values()), key
+        ref.close()
+
+
 def test_cameras_see_the_objects(frames):
     """at least 70 % of the scenes with instances have a first-pass hit share of at least 0.1"""
     shares = [frames[s]["hit"] for s in G.SEEDS if G.flat_scene(s)[3].instances]
@@ -104,6 +122,49 @@ def test_oracle_against_itself_is_exact(built, mode):
         r = lockstep.lockstep(OracleDevice(dev, threads=4), ref, G.PASSES)
         dev.close(), ref.close()
         assert r["exact"] == r["segments"] and bad(r) == 0 and r["depth_mismatch"] == 0, (seed, lockstep.describe(r))
+
+
+def test_packaging_sweep_comparison_on_the_oracle(built):
+    """The comparison of tests/test_packaging_sweep_gpu.py (tests/packaging_sweep.py) with the oracle in the device's place, on the first 10
+    scenes: the plain oracle through the call patterns (8,), (1, 2, 5) and (3, 5) equals its own pass-by-pass render — accumulator, depth,
+    path state, ray and pass counts after 1, 3 and 8 passes —, and the "lo" libm stand-in as the variant is reported different on at
+    least one scene (the comparison can fail)."""
+    import packaging_sweep as S
+    flagged = []
+    for seed in G.SEEDS[:10]:
+        base = _renderer(seed)
+        want = S.pass_by_pass(OracleDevice(base))
+        base.close()
+        assert sorted(want) == list(S.KEPT) and want[8]["passes"] == 8 and want[3]["rays"] == 3 * want[1]["rays"] > 0
+        same, lo = _renderer(seed), _renderer(seed, lib=oracle.variant("lo"))
+        assert S.compare_patterns(OracleDevice(same, threads=4), want) == [], seed
+        if S.compare_patterns(OracleDevice(lo), want):
+            flagged.append(seed)
+        same.close(), lo.close()
+    print(f"packaging sweep comparison: the 'lo' stand-in differs from the plain oracle on scenes {flagged}")
+    assert flagged
+
+
+def test_packaging_sweep_comparison_names_what_differs(built):
+    """one changed value in one snapshot — a pixel's accumulator, a path depth, the ray count — is reported with its pass count and name"""
+    import packaging_sweep as S
+    ref = _renderer(0)
+    want = S.pass_by_pass(OracleDevice(ref))
+    ref.close()
+    assert S.differences(want, want) == []
+    for name, change in (("accum", lambda v: np.nextafter(v, np.float32(np.inf))), ("state.depth", lambda v: v + 1), ("state.origin", lambda v: -v),
+                         ("depth", lambda v: np.nextafter(v, np.float32(0)))):
+        got = {n: dict(snap) for n, snap in want.items()}
+        got[3][name] = want[3][name].copy()
+        got[3][name].reshape(-1)[5] = change(got[3][name].reshape(-1)[5])
+        assert [(p, f) for p, f, _ in S.differences(got, want)] == [(3, name)], name
+    got = {n: dict(snap) for n, snap in want.items()}
+    got[8]["rays"] += 1
+    assert [(p, f) for p, f, _ in S.differences(got, want)] == [(8, "rays")]
+    nan = {n: dict(snap) for n, snap in want.items()}
+    nan[1]["accum"] = want[1]["accum"].copy()
+    nan[1]["accum"][0, 0, 0] = np.nan
+    assert S.differences(nan, nan) == [] and [(p, f) for p, f, _ in S.differences(nan, want)] == [(1, "accum")]
 
 
 def test_adopt_continues_a_frame(built):
