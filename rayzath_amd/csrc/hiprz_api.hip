@@ -113,6 +113,77 @@ __global__ void __launch_bounds__(256) rz_selftest_div_kernel(uint32_t n_per_thr
                 if ((hit && !exact) || (missed && exact) || (hit && missed)) bad += 1;
                 if (!hit && !missed) undecided += 1;
             }
+            // (The two comparisons below run on every case and report into `bad`; `tested` stays the count of quotients and filtered box
+            // tests, which tests/test_parity_gpu.py bounds from both sides.)
+            // the one-leaf walk's packed box test (RZ_FLAT_PACKED_BOXES): tmin and tmax of the packed sequences (box_range_pairs, what
+            // box_range_packed runs for a wave of fast rays) are box_range_unpacked's, bit for bit.  Called directly, so that the comparison
+            // is there whichever way the switch stands; a ray that is not fast takes box_range_unpacked<false> under either setting.
+            if (r.fast) {
+                float tmin_p, tmax_p, tmin_u, tmax_u;
+                box_range_pairs(b0, b1, splat_pairs(r), tmin_p, tmax_p);
+                box_range_unpacked<true>(b0, b1, r, tmin_u, tmax_u);
+                if (__float_as_uint(tmin_p) != __float_as_uint(tmin_u) || __float_as_uint(tmax_p) != __float_as_uint(tmax_u)) bad += 1;
+            }
+            // the one-leaf walk's triangle loop: two triangles in one iteration (tri_pair_step: tri_hit2 + pair_pick) against the
+            // one-by-one loop (tri_hit, the far end moving between the two) — far end, winner, b1, b2 and the facing bit.  Random pairs
+            // in front of the ray, and by the bits of `kind`: the same triangle twice (equal distances: the first wins), a ray almost in
+            // the triangle's plane (|det| < 1e-7: the nudge), an origin in the plane (t = 0), and a near or far end that IS a hit's t.
+            {
+                const uint32_t kind = (h >> 4) & 7u;
+                float4 ta[3], tb[3];
+                auto corner = [&](uint32_t k, float depth) { return V3(unit(k) * 6.0f - 3.0f, unit(k + 1u) * 6.0f - 3.0f, depth); };
+                auto make = [&](float4 (&rec)[3], uint32_t k, float depth) {
+                    const v3 p1 = corner(k, depth + unit(k + 6u)), p2 = corner(k + 2u, depth + unit(k + 7u)), p3 = corner(k + 4u, depth + unit(k + 8u));
+                    const v3 e1 = p2 - p1, e2 = p3 - p1;
+                    rec[0] = make_float4(p1.x, p1.y, p1.z, 0.0f), rec[1] = make_float4(e1.x, e1.y, e1.z, 0.0f), rec[2] = make_float4(e2.x, e2.y, e2.z, 0.0f);
+                };
+                make(ta, 20u, 2.0f), make(tb, 30u, (h & 0x100u) ? 2.0f : 3.0f);
+                if (kind == 1u) tb[0] = ta[0], tb[1] = ta[1], tb[2] = ta[2];
+                WalkRay q;
+                q.o = V3(unit(40) * 2.0f - 1.0f, unit(41) * 2.0f - 1.0f, -1.0f);
+                const v3 aim = V3(unit(42) * 4.0f - 2.0f, unit(43) * 4.0f - 2.0f, 2.5f);
+                q.d = normalized(aim - q.o), q.near_ = 0.0f, q.far_ = (h & 0x200u) ? RZ_FLT_MAX : 8.0f;
+                if (kind == 2u) {  // almost in a's plane: along edge1, tilted towards the normal by up to 2e-8
+                    const v3 e1 = xyz(ta[1]), nrm = cross(xyz(ta[1]), xyz(ta[2]));
+                    q.d = normalized(normalized(e1) + normalized(nrm) * ((unit(44) - 0.5f) * 4.0e-8f));
+                }
+                if (kind == 3u) q.o = xyz(ta[0]) + xyz(ta[1]) * (unit(45) * 0.5f) + xyz(ta[2]) * (unit(46) * 0.5f);  // in a's plane
+                q.fast = false, q.y = V3(0.0f, 0.0f, 0.0f);
+                if (kind >= 4u) {  // a range end on a hit's distance: a's (4, 5) or b's (6, 7), near (even) or far (odd)
+                    const bool of_a = kind < 6u;
+                    WalkRay probe = q;
+                    probe.far_ = RZ_FLT_MAX;
+                    float t = 0.0f, u, v, det;
+                    if (tri_hit(xyz(of_a ? ta[0] : tb[0]), xyz(of_a ? ta[1] : tb[1]), xyz(of_a ? ta[2] : tb[2]), probe, t, u, v, det)) {
+                        if (kind & 1u) q.far_ = t;
+                        else q.near_ = t;
+                    }
+                }
+                const bool has_b = (h & 0xC00u) != 0u;  // every fourth case: a lone triangle in the iteration
+                // one by one
+                WalkRay seq = q;
+                uint32_t seq_tri = 0xFFFFFFFFu;
+                float seq_b1 = 0.0f, seq_b2 = 0.0f;
+                bool seq_external = false;
+                {
+                    float t, u, v, det;
+                    if (tri_hit(xyz(ta[0]), xyz(ta[1]), xyz(ta[2]), seq, t, u, v, det)) {
+                        seq.far_ = t;
+                        seq_tri = 0u, seq_b1 = u, seq_b2 = v, seq_external = det > 0.0f;
+                    }
+                    if (has_b && tri_hit(xyz(tb[0]), xyz(tb[1]), xyz(tb[2]), seq, t, u, v, det)) {
+                        seq.far_ = t;
+                        seq_tri = 1u, seq_b1 = u, seq_b2 = v, seq_external = det > 0.0f;
+                    }
+                }
+                // as a pair
+                LeafBest best;
+                best.far_ = q.far_, best.triangle = 0xFFFFFFFFu, best.b1 = best.b2 = 0.0f, best.external = false;
+                tri_pair_step(ta[0], ta[1], ta[2], has_b ? tb[0] : ta[0], has_b ? tb[1] : ta[1], has_b ? tb[2] : ta[2], 0u, has_b ? 1u : 0u, has_b, q, best);
+                if (__float_as_uint(best.far_) != __float_as_uint(seq.far_) || best.triangle != seq_tri || __float_as_uint(best.b1) != __float_as_uint(seq_b1) ||
+                    __float_as_uint(best.b2) != __float_as_uint(seq_b2) || best.external != seq_external)
+                    bad += 1;
+            }
         }
     }
     atomicAdd(&out[0], (unsigned long long)bad);

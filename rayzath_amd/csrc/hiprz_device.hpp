@@ -18,6 +18,7 @@
 
 #define RZ_DEV __device__ __forceinline__
 #include "hiprz_flat_pick.hpp"
+#include "hiprz_pair_pick.hpp"
 
 namespace hiprz {
 
@@ -30,6 +31,12 @@ namespace hiprz {
 #endif
 #ifndef RZ_BATCH_SHARED_RCP   // ... in the resident pipeline's batch kernel
 #define RZ_BATCH_SHARED_RCP 1
+#endif
+#ifndef RZ_FLAT_PACKED_BOXES   // one-leaf walk (closest_hit_flat): the up-front instance boxes, the root box and the visits' mesh box on register pairs
+#define RZ_FLAT_PACKED_BOXES 0 // off: measured alone it loses 2.1 % on config B, and it takes 2.5 % from the triangle pairs (profiles/r13)
+#endif
+#ifndef RZ_FLAT_PAIR_TRIS      // one-leaf walk: the triangles of a leaf tested two at a time on float2 vectors (tri_hit2)
+#define RZ_FLAT_PAIR_TRIS 1    // on: +3.9 % on config B measured alone
 #endif
 #ifndef RZ_TRACE_MIN_WAVES
 #define RZ_TRACE_MIN_WAVES 5
@@ -533,6 +540,107 @@ RZ_DEV bool tri_hit(v3 v1, v3 edge1, v3 edge2, const WalkRay& r, float& t, float
     return tri_hit(v1, edge1, edge2, q, t, b1, b2, det);
 }
 
+// ---- packed forms for the one-leaf walk (closest_hit_flat): two IEEE fp32 operations per lane and instruction ----
+// v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 round each half exactly like their one-float twins, and -ffp-contract=off keeps every
+// multiply and add apart: a packed sequence is the unpacked one, twice.  hiprz_selftest compares both forms below bit for bit.
+
+// The ray of a box test as register pairs (origin, negated direction, refined reciprocal, each splat): built where a run of box tests
+// starts and dead where it ends — the pairs are 18 registers that must not live across a round.
+struct WalkRayPairs {
+    f2 ox, oy, oz, ndx, ndy, ndz, yx, yy, yz;
+};
+RZ_DEV WalkRayPairs splat_pairs(const WalkRay& r) {
+    WalkRayPairs p;
+    p.ox = f2{r.o.x, r.o.x}, p.oy = f2{r.o.y, r.o.y}, p.oz = f2{r.o.z, r.o.z};
+    p.ndx = f2{-r.d.x, -r.d.x}, p.ndy = f2{-r.d.y, -r.d.y}, p.ndz = f2{-r.d.z, -r.d.z};
+    p.yx = f2{r.y.x, r.y.x}, p.yy = f2{r.y.y, r.y.y}, p.yz = f2{r.y.z, r.y.z};
+    return p;
+}
+RZ_DEV f2 div_pairs(f2 n, f2 nd, f2 yy) {  // div_shared2 on pairs that exist already
+    f2 q = n * yy;
+    f2 r = __builtin_elementwise_fma(nd, q, n);
+    q = __builtin_elementwise_fma(r, yy, q);
+    r = __builtin_elementwise_fma(nd, q, n);
+    return __builtin_elementwise_fma(r, yy, q);
+}
+// the fast path of box_range_unpacked, its six quotients as three packed sequences (box_hit's): r.fast lanes only
+RZ_DEV void box_range_pairs(float4 b0, float4 b1, const WalkRayPairs& p, float& tmin, float& tmax) {
+    const f2 tx = div_pairs(f2{b0.x, b0.y} - p.ox, p.ndx, p.yx);
+    const f2 ty = div_pairs(f2{b0.z, b0.w} - p.oy, p.ndy, p.yy);
+    const f2 tz = div_pairs(f2{b1.x, b1.y} - p.oz, p.ndz, p.yz);
+    tmin = vmax3(vmin(tx.x, tx.y), vmin(ty.x, ty.y), vmin(tz.x, tz.y));
+    tmax = vmin3(vmax(tx.x, tx.y), vmax(ty.x, ty.y), vmax(tz.x, tz.y));
+}
+// box_range_unpacked's tmin and tmax, bit for bit
+template <bool SHARED_RCP>
+RZ_DEV void box_range_packed(float4 b0, float4 b1, const WalkRay& r, float& tmin, float& tmax) {
+#if RZ_FLAT_PACKED_BOXES
+    if (SHARED_RCP && __all(r.fast)) {  // wave-uniform branch
+        box_range_pairs(b0, b1, splat_pairs(r), tmin, tmax);
+        return;
+    }
+    box_range_unpacked<false>(b0, b1, r, tmin, tmax);
+#else
+    box_range_unpacked<SHARED_RCP>(b0, b1, r, tmin, tmax);
+#endif
+}
+template <bool SHARED_RCP>
+RZ_DEV bool box_hit_packed(float4 b0, float4 b1, const WalkRay& r) {
+    float tmin, tmax;
+    box_range_packed<SHARED_RCP>(b0, b1, r, tmin, tmax);
+    return !(tmax < r.near_ || tmin > tmax || tmin > r.far_);
+}
+
+// Moller-Trumbore on two triangles at once: element 0 = triangle a, element 1 = triangle b of the same leaf, against the same ray.
+// Every element performs tri_hit's operations in tri_hit's order — the det nudge element by element, two true divisions — except that
+// nothing returns early and that the far end is left to pair_pick (hiprz_pair_pick.hpp).  inside_a / inside_b: the triangle is hit
+// somewhere beyond the near end.
+struct v3p {
+    f2 x, y, z;
+};
+RZ_DEV v3p pair3(float4 a, float4 b) { return v3p{f2{a.x, b.x}, f2{a.y, b.y}, f2{a.z, b.z}}; }
+RZ_DEV float det_nudge(float det) { return float(uint32_t(det > -1.0e-7f) & uint32_t(det < 1.0e-7f)) * 1.0e-7f; }
+RZ_DEV void tri_hit2(v3p v1, v3p edge1, v3p edge2, const WalkRay& r, bool& inside_a, bool& inside_b, f2& t_out, f2& b1_out, f2& b2_out, f2& det_out) {
+    const f2 dx = {r.d.x, r.d.x}, dy = {r.d.y, r.d.y}, dz = {r.d.z, r.d.z};
+    const v3p pvec = {dy * edge2.z - dz * edge2.y, dz * edge2.x - dx * edge2.z, dx * edge2.y - dy * edge2.x};
+    f2 det = edge1.x * pvec.x + edge1.y * pvec.y + edge1.z * pvec.z;
+    det = det + f2{det_nudge(det.x), det_nudge(det.y)};
+    const f2 inv_det = {1.0f / det.x, 1.0f / det.y};
+    const v3p tvec = {f2{r.o.x, r.o.x} - v1.x, f2{r.o.y, r.o.y} - v1.y, f2{r.o.z, r.o.z} - v1.z};
+    const f2 b1 = (tvec.x * pvec.x + tvec.y * pvec.y + tvec.z * pvec.z) * inv_det;
+    const v3p qvec = {tvec.y * edge1.z - tvec.z * edge1.y, tvec.z * edge1.x - tvec.x * edge1.z, tvec.x * edge1.y - tvec.y * edge1.x};
+    const f2 b2 = (dx * qvec.x + dy * qvec.y + dz * qvec.z) * inv_det;
+    const f2 sum = b1 + b2;
+    const f2 t = (edge2.x * qvec.x + edge2.y * qvec.y + edge2.z * qvec.z) * inv_det;
+    // (no early way out: a wave of dense items never has all its lanes outside both triangles after b1, and the branch costs more than it skips)
+    inside_a = !(b1.x < 0.0f || b1.x > 1.0f) && !(b2.x < 0.0f || sum.x > 1.0f) && !(t.x <= r.near_);
+    inside_b = !(b1.y < 0.0f || b1.y > 1.0f) && !(b2.y < 0.0f || sum.y > 1.0f) && !(t.y <= r.near_);
+    t_out = t, b1_out = b1, b2_out = b2, det_out = det;
+}
+// what a leaf's triangle loop carries from one triangle to the next: the far end of the range and the hit that set it
+struct LeafBest {
+    float far_;
+    uint32_t triangle;  // 0xFFFFFFFF: none yet
+    float b1, b2;
+    bool external;
+};
+// One iteration of a leaf's loop on triangles ia and ib (records a*, b*; ib stands behind ia in leaf order and only counts where
+// has_b): what two iterations of the one-by-one loop leave in `best`.
+RZ_DEV void tri_pair_step(float4 a0, float4 a1, float4 a2, float4 b0, float4 b1, float4 b2, uint32_t ia, uint32_t ib, bool has_b,
+                          const WalkRay& r, LeafBest& best) {
+    f2 t, u, v, det;
+    bool inside_a, inside_b;
+    tri_hit2(pair3(a0, b0), pair3(a1, b1), pair3(a2, b2), r, inside_a, inside_b, t, u, v, det);
+    const PairPick pick = pair_pick(inside_a, inside_b && has_b, t.x, t.y, best.far_);
+    best.far_ = pick.far_;
+    if (pick.winner != 0u) {
+        const bool second = pick.winner == 2u;
+        best.triangle = second ? ib : ia;
+        best.b1 = second ? u.y : u.x, best.b2 = second ? v.y : v.x;
+        best.external = (second ? det.y : det.x) > 0.0f;
+    }
+}
+
 // ---- MODE 1: nested loops with an LDS stack ----
 struct LdsStack {
     uint32_t* column;  // this lane's column: entry k lives at column[k * blockDim.x]
@@ -794,6 +902,25 @@ RZ_DEV FlatWorld make_flat_world(const DScene& s) {
 template <bool COUNT, bool RCP>
 RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, const WalkRay& g, float (&tm)[8], bool counting, Counters& cnt) {
     uint32_t mask = 0u;
+#if RZ_FLAT_PACKED_BOXES
+    if (RCP && __all(g.fast)) {  // wave-uniform branch: the ray's pairs are built once for the eight boxes and end with them
+        const WalkRayPairs gp = splat_pairs(g);
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            tm[k] = 0.0f;
+            if (k < fw.count) {  // scalar
+                float4 ib0, ib1;
+                load_instance_box(s, flat_id(fw.ids, k), ib0, ib1);
+                float tmin, tmax;
+                box_range_pairs(ib0, ib1, gp, tmin, tmax);
+                if (counting) { RZ_PHASE(1); RZ_COUNT(box_tests); }
+                mask |= uint32_t(!(tmax < g.near_ || tmin > tmax)) << k;
+                tm[k] = tmin;
+            }
+        }
+        return mask;
+    }
+#endif
 #pragma unroll
     for (uint32_t k = 0; k < 8u; ++k) {
         tm[k] = 0.0f;
@@ -801,7 +928,7 @@ RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, con
             float4 ib0, ib1;
             load_instance_box(s, flat_id(fw.ids, k), ib0, ib1);
             float tmin, tmax;
-            box_range_unpacked<RCP>(ib0, ib1, g, tmin, tmax);
+            box_range_unpacked<RZ_FLAT_PACKED_BOXES ? false : RCP>(ib0, ib1, g, tmin, tmax);
             if (counting) { RZ_PHASE(1); RZ_COUNT(box_tests); }
             mask |= uint32_t(!(tmax < g.near_ || tmin > tmax)) << k;
             tm[k] = tmin;
@@ -824,6 +951,53 @@ RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_c
     const InstanceXform x = load_instance_xform(s, inst);
     WalkRay lr;
     const float len = to_local<RCP>(x, w, lr, scene_fast);
+#if RZ_FLAT_PAIR_TRIS
+    // A mesh that is one leaf, whether 8 lanes share the visit or one lane has it: ONE loop, two triangles per iteration (tri_pair_step).
+    // Lane j of an octet pairs triangles (i, i + 8) from i = j on in steps of 16; a lane on its own pairs (i, i + 1).  The second of a
+    // pair stands behind the first in leaf order, and a lane's pairs follow one another in leaf order: the lane ends with what the
+    // one-by-one loop over its triangles ends with, and an octet's lanes are merged as before.
+    const float4 n0 = s.nodes[2 * x.blas_root], n1 = s.nodes[2 * x.blas_root + 1];
+    const bool wide = (item & RZ_BIN_WIDE) != 0u;
+    if (wide || (__float_as_uint(n1.w) & HIPRZ_NODE_LEAF) != 0u) {
+        const uint32_t j = wide ? slot & 7u : 0u, partner = wide ? 8u : 1u;
+        RZ_PHASE(3);
+        if (j == 0u) { RZ_COUNT(box_tests); }  // once per visit
+        LeafBest best;
+        best.far_ = lr.far_, best.triangle = 0xFFFFFFFFu, best.b1 = best.b2 = 0.0f, best.external = false;
+        if (box_hit_packed<RCP>(n0, n1, lr)) {
+            const uint32_t begin = __float_as_uint(n1.z), end = begin + (__float_as_uint(n1.w) & HIPRZ_NODE_COUNT_MASK);
+            for (uint32_t i = begin + j; i < end; i += 2u * partner) {
+                const bool has_b = i + partner < end;
+                const uint32_t ib = has_b ? i + partner : i;  // (a lone triangle is loaded twice: no record past the leaf is touched)
+                const float4 a0 = s.tris[3 * i], a1 = s.tris[3 * i + 1], a2 = s.tris[3 * i + 2];
+                const float4 b0 = s.tris[3 * ib], b1 = s.tris[3 * ib + 1], b2 = s.tris[3 * ib + 2];
+                RZ_PHASE(4);
+                if constexpr (COUNT) cnt.tri_tests += has_b ? 2u : 1u;
+                tri_pair_step(a0, a1, a2, b0, b1, b2, i, ib, has_b, lr, best);
+            }
+        }
+        bool mine = best.triangle != 0xFFFFFFFFu;
+        if (wide) {
+            // the octet's winner hands the visit's hit to the ray's slot (the 8 lanes of a visit take this branch together; distances
+            // are positive: their bits order like they do)
+            const uint32_t wide_t = mine ? __float_as_uint(best.far_) : 0xFFFFFFFFu;
+            const uint32_t t_min = octet_min(wide_t);
+            const bool nearest = wide_t != 0xFFFFFFFFu && wide_t == t_min;
+            const uint32_t first = octet_min(nearest ? best.triangle : 0xFFFFFFFFu);
+            mine = nearest && best.triangle == first;
+        }
+        if (mine) {
+            lds.ray[6 * 256 + src] = lr.near_ / len;
+            lds.ray[7 * 256 + src] = best.far_ / len;
+            lds.hit[0 * 256 + src] = best.triangle;
+            lds.hit[1 * 256 + src] = best.external ? 1u : 0u;
+            lds.hit[2 * 256 + src] = __float_as_uint(best.b1);
+            lds.hit[3 * 256 + src] = __float_as_uint(best.b2);
+            lds.hit[4 * 256 + src] = inst;
+        }
+        return;
+    }
+#endif
     if (item & RZ_BIN_WIDE) {
         // the mesh is one leaf: its box once per visit (counted by lane 0 of the octet), then this lane's share of its triangles —
         // each against the range the visit started with, shortened by this lane's own earlier hits; the octet's minimum below is
@@ -836,7 +1010,7 @@ RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_c
         float wide_b1 = 0.0f, wide_b2 = 0.0f;
         bool wide_external = false;
         const float visit_near = lr.near_;
-        if (box_hit_unpacked<RCP>(n0, n1, lr)) {
+        if (box_hit_packed<RCP>(n0, n1, lr)) {
             const uint32_t begin = __float_as_uint(n1.z), end = begin + (__float_as_uint(n1.w) & HIPRZ_NODE_COUNT_MASK);
             for (uint32_t i = begin + j; i < end; i += 8u) {
                 const float4 a = s.tris[3 * i], b = s.tris[3 * i + 1], cc = s.tris[3 * i + 2];
@@ -1129,7 +1303,7 @@ __device__ __forceinline__ int closest_hit_flat(const DScene& s, const FlatWorld
     if (active) {
         RZ_PHASE(0);
         RZ_COUNT(box_tests);
-        if (box_hit_unpacked<RCP>(fw.root0, fw.root1, g)) flat_mask = pretest_leaf_instances<COUNT, RCP>(s, fw, g, tm, true, cnt);
+        if (box_hit_packed<RCP>(fw.root0, fw.root1, g)) flat_mask = pretest_leaf_instances<COUNT, RCP>(s, fw, g, tm, true, cnt);
         else root_missed = true;
     }
     // both halves of the double-buffered bins: the round that left the previous call found its own half empty and left the other one,
