@@ -1,0 +1,244 @@
+"""The two device mesh-tree builders of rayzath_amd/csrc/hiprz_build.hip restated in numpy float32, one rounding per operation, from the
+algorithms' definitions (no GPU, no library call).  The library is compiled without contraction and with correctly rounded division, so
+every float the kernels compute is a function of the mesh that these functions reproduce bit for bit; the structure is deliberately
+another one (recursions over triangle sets, vectorised scans with infinite sentinels, one search per range instead of one per node).
+
+  morton_tree(tris, lo, hi)  Morton order: keys of the centroids on the 1024^3 grid of the mesh box, a stable sort, the binary radix tree
+                             over the keys made distinct by their position, ranges of at most 4 triangles collapsed into leaves.
+  sah_tree(tris, lo, hi)     binned surface-area build: 16 bins per axis; nodes of more than 32 triangles bin over the box their parent
+                             handed them and always split; smaller subtrees start in ascending triangle order and follow the leaf rule.
+
+`tris` are the mesh's triangles (records with v1, v2, v3) in the order they have before the build, `lo` / `hi` the mesh box the build is
+given.  Both return a RefTree: `order[p]` = index before the build of the triangle at position p afterwards, and the nodes.
+pack_nodes() lays a RefTree out as node records with exact boxes."""
+import numpy as np
+
+F = np.float32
+LEAF, PTYPE_SHIFT = 0x80000000, 29
+node_dtype = np.dtype([("bb_min", "<f4", 3), ("bb_max", "<f4", 3), ("begin", "<u4"), ("meta", "<u4")])
+MORTON_LEAF, SAH_LEAF, SAH_SMALL, SAH_BINS = 4, 8, 32, 16
+
+
+class RefNode:
+    __slots__ = ("first", "count", "ptype", "kids")
+
+    def __init__(self, first, count, ptype=None, kids=None):
+        self.first, self.count, self.ptype, self.kids = first, count, ptype, kids   # ptype None: a leaf
+
+
+class RefTree:
+    def __init__(self, order, root, order_dependent=False):
+        self.order, self.root = np.asarray(order, dtype=np.int64), root
+        self.order_dependent = order_dependent   # a node of more than 32 coincident centres below the root was halved: the device cuts it as its
+                                                 # run stands, in an order that wave scheduling decides
+
+    def walk(self):
+        stack = [self.root]
+        while stack:
+            n = stack.pop()
+            yield n
+            if n.kids:
+                stack += [n.kids[1], n.kids[0]]
+
+    def node_set(self):
+        """{(first, count, leaf?, partition type, first child's first, first child's count)}: with `order`, every node's triangles in leaf
+        order and its children's order, free of slot numbers."""
+        return {(n.first, n.count, n.kids is None, -1 if n.kids is None else n.ptype) + ((n.kids[0].first, n.kids[0].count) if n.kids else (-1, -1))
+                for n in self.walk()}
+
+
+def triangle_boxes(tris):
+    v = np.stack([tris["v1"], tris["v2"], tris["v3"]], 1).astype(F)
+    return v.min(1), v.max(1)
+
+
+# ---------------------------------------------------------------- Morton order
+def morton_keys(tris, lo, hi):
+    v1, v2, v3 = (np.asarray(tris[k], dtype=F) for k in ("v1", "v2", "v3"))
+    lo, hi = np.asarray(lo, dtype=F), np.asarray(hi, dtype=F)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        c = v1 + ((v2 - v1) + (v3 - v1)) * (F(1) / F(3))
+        scale = np.where(hi > lo, F(1024) / (hi - lo), F(0)).astype(F)
+        cell = np.minimum(np.maximum((c - lo) * scale, F(0)), F(1023)).astype(np.uint32)
+    key = np.zeros(len(cell), dtype=np.uint32)
+    for bit in range(9, -1, -1):   # x, y, z from high to low
+        for axis in range(3):
+            key = (key << np.uint32(1)) | ((cell[:, axis] >> np.uint32(bit)) & np.uint32(1))
+    return key
+
+
+def morton_tree(tris, lo, hi, keep_four=False):
+    """keep_four: (a mutant for the tests) the first range of exactly 4 triangles is split instead of collapsed."""
+    n = len(tris)
+    keys = morton_keys(tris, lo, hi)
+    order = np.argsort(keys, kind="stable")
+    aug = [(int(k) << 32) | p for p, k in enumerate(keys[order].tolist())]
+    tmn, tmx = triangle_boxes(tris[order])
+
+    def build(a, b):   # positions a .. b inclusive
+        count = b - a + 1
+        nonlocal keep_four
+        if count <= MORTON_LEAF and not (keep_four and count == MORTON_LEAF):
+            return RefNode(a, count)
+        if count == MORTON_LEAF:
+            keep_four = False
+        top = (aug[a] ^ aug[b]).bit_length() - 1
+        s, above = a, b   # s -> the last position with a 0 in bit `top` (the keys ascend: the zeros come first)
+        while s < above:
+            mid = (s + above + 1) // 2
+            if (aug[mid] >> top) & 1:
+                above = mid - 1
+            else:
+                s = mid
+        box = lambda p, q: (tmn[p:q + 1].min(0), tmx[p:q + 1].max(0))
+        (lmn, lmx), (rmn, rmx) = box(a, s), box(s + 1, b)
+        cl, cr = lmn + lmx, rmn + rmx
+        axis = int(np.argmax(np.abs(cl - cr)))
+        kids = (build(a, s), build(s + 1, b))
+        if cl[axis] > cr[axis]:
+            kids = kids[::-1]
+        return RefNode(a, count, 2 - axis, kids)
+    return RefTree(order, build(0, n - 1))
+
+
+# ---------------------------------------------------------------- binned surface-area build
+def _area(mn, mx):
+    d = mx - mn
+    return d[..., 0] * d[..., 1] + d[..., 1] * d[..., 2] + d[..., 2] * d[..., 0]
+
+
+def _bins(c, lo, hi):
+    """bin of every centre c on one axis of the box lo .. hi, or None when the axis is flat (every centre in bin 0: no plane)"""
+    if not hi > lo:
+        return None
+    scale = F(SAH_BINS) / (hi - lo)
+    return np.clip(np.trunc((c - lo) * scale), 0, SAH_BINS - 1).astype(np.int64)
+
+
+def _best_plane(cen, tmn, tmx, lo, hi):
+    """The plane of least cost area_l * n_l + area_r * n_r over axes 0..2 and planes 1..15 (first strict minimum), binning the centres
+    over lo .. hi: (cost, axis, plane, bins on that axis) or None when no plane has triangles on both sides."""
+    costs, bins = [], []
+    inf = F(np.inf)
+    for a in range(3):
+        b = _bins(cen[:, a], lo[a], hi[a])
+        bins.append(b)
+        if b is None:
+            costs.append(np.full(SAH_BINS - 1, inf, dtype=F))
+            continue
+        cnt = np.bincount(b, minlength=SAH_BINS)
+        bmn, bmx = np.full((SAH_BINS, 3), inf, dtype=F), np.full((SAH_BINS, 3), -inf, dtype=F)
+        np.minimum.at(bmn, b, tmn), np.maximum.at(bmx, b, tmx)
+        ln, rn = np.cumsum(cnt)[:-1], np.cumsum(cnt[::-1])[::-1][1:]           # plane p: bins 0 .. p-1 | bins p .. 15
+        with np.errstate(invalid="ignore", over="ignore"):
+            la = _area(np.minimum.accumulate(bmn)[:-1], np.maximum.accumulate(bmx)[:-1])
+            ra = _area(np.minimum.accumulate(bmn[::-1])[::-1][1:], np.maximum.accumulate(bmx[::-1])[::-1][1:])
+            cost = (la * ln.astype(F) + ra * rn.astype(F)).astype(F)
+        cost[~((ln > 0) & (rn > 0) & (cost < F(3.4e38)))] = inf
+        costs.append(cost)
+    costs = np.concatenate(costs)
+    k = int(np.argmin(costs))
+    if not costs[k] < inf:
+        return None
+    axis, plane = divmod(k, SAH_BINS - 1)
+    return costs[k], axis, plane + 1, bins[axis]
+
+
+def sah_tree(tris, lo, hi, leaf_max=SAH_LEAF, traversal=F(4.0), root_plane_shift=0):
+    """root_plane_shift: (a mutant for the tests) the root's plane moved by so many bins."""
+    n = len(tris)
+    tmn, tmx = triangle_boxes(tris)
+    cen = ((tmn + tmx) * F(0.5)).astype(F)
+    order, halved = [], [False]
+
+    def leaf(run):
+        node = RefNode(len(order), len(run))
+        order.extend(run)
+        return node
+
+    def inner(ptype, make_left, make_right, count):
+        first = len(order)
+        left = make_left()
+        return RefNode(first, count, ptype, (left, make_right()))
+
+    def small(run):   # a subtree of at most 32 triangles; `run` is a list, in the order the partition left it in
+        count = len(run)
+        if count <= 2:
+            return leaf(run)
+        ix = np.asarray(run)
+        c, mn, mx = cen[ix], tmn[ix], tmx[ix]
+        best = _best_plane(c, mn, mx, c.min(0), c.max(0))
+        area = _area(mn.min(0), mx.max(0))
+        with np.errstate(over="ignore"):
+            split_cost = traversal + best[0] / area if best is not None and area > 0 else F(3.4e38)
+        if count <= leaf_max and F(count) <= split_cost:
+            return leaf(run)
+        if best is None:   # every centre in one spot: halve the run as it stands
+            mid, ptype = count // 2, 3
+        else:
+            _, axis, plane, b = best
+            below = dict(zip(run, (b < plane).tolist()))
+            run, i, j = list(run), 0, count
+            while i < j:   # the two-pointer partition fixes the leaf order
+                if below[run[i]]:
+                    i += 1
+                else:
+                    j -= 1
+                    run[i], run[j] = run[j], run[i]
+            mid, ptype = i, 2 - axis
+        return inner(ptype, lambda: small(run[:mid]), lambda: small(run[mid:]), count)
+
+    def large(ix, lo, hi, shift=0, root=False):   # more than 32 triangles (ix ascending): always splits, binning over the box it was handed
+        if len(ix) <= SAH_SMALL:
+            return small(ix.tolist())
+        best = _best_plane(cen[ix], tmn[ix], tmx[ix], lo, hi)
+        if best is None:   # no plane separates anything: the run is halved as it stands (the root's run stands in triangle order)
+            halved[0] = halved[0] or not root
+            mid = len(ix) // 2
+            return inner(3, lambda: large(ix[:mid], lo, hi), lambda: large(ix[mid:], lo, hi), len(ix))
+        _, axis, plane, b = best
+        below = b < plane + shift
+        l, r = ix[below], ix[~below]
+        assert len(l) and len(r)
+        return inner(2 - axis, lambda: large(l, tmn[l].min(0), tmx[l].max(0)), lambda: large(r, tmn[r].min(0), tmx[r].max(0)), len(ix))
+
+    root = large(np.arange(n), np.asarray(lo, dtype=F), np.asarray(hi, dtype=F), root_plane_shift, True)
+    return RefTree(order, root, halved[0])
+
+
+# ---------------------------------------------------------------- node records
+def pack_nodes(tree, tris_in_order, slot_base=0, tri_first=0):
+    """The RefTree as node records: root at `slot_base`, the children of a node adjacent with the first child first, leaves pointing at
+    tri_first + position, every box the exact min / max of the triangles below (`tris_in_order` = the mesh's triangles after the build)."""
+    tmn, tmx = triangle_boxes(tris_in_order)
+    todo, slots = [(tree.root, slot_base)], 1
+    out = {}
+    while todo:
+        n, slot = todo.pop()
+        rec = np.zeros((), dtype=node_dtype)
+        rec["bb_min"], rec["bb_max"] = tmn[n.first:n.first + n.count].min(0), tmx[n.first:n.first + n.count].max(0)
+        if n.kids is None:
+            rec["begin"], rec["meta"] = tri_first + n.first, LEAF | n.count
+        else:
+            rec["begin"], rec["meta"] = slot_base + slots, n.ptype << PTYPE_SHIFT
+            todo += [(n.kids[0], slot_base + slots), (n.kids[1], slot_base + slots + 1)]
+            slots += 2
+        out[slot] = rec
+    return np.array([out[slot_base + k] for k in range(slots)], dtype=node_dtype)
+
+
+def differences(ref, nodes, root, local_order, tri_first=0):
+    """What a downloaded tree (node table, root, `local_order[p]` = index before the build of the mesh's triangle at position p) and the
+    RefTree disagree on — empty when they are the same tree: the same triangle order and the same set of nodes, each with its triangles
+    in leaf order, its partition type and its first child (never slot numbers, which an atomic counter hands out)."""
+    from tree_audit import node_set
+    out = []
+    local_order = np.asarray(local_order, dtype=np.int64)
+    if not np.array_equal(local_order, ref.order):
+        bad = np.flatnonzero(local_order != ref.order)
+        out.append(f"triangle order differs at {len(bad)} of {len(ref.order)} positions, first at {int(bad[0])}: {int(local_order[bad[0]])}, reference {int(ref.order[bad[0]])}")
+    have, want = node_set(nodes, root, tri_first), ref.node_set()
+    if have != want:
+        out.append(f"nodes differ: {len(have - want)} only downloaded, {len(want - have)} only in the reference, e.g. {sorted(have - want)[:2]} / {sorted(want - have)[:2]}"
+                   " (first, count, leaf, partition type, first child's first, count)")
+    return out
