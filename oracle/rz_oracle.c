@@ -352,26 +352,44 @@ static inline v3 transform_l2g_noscale(const hiprz_instance* in, v3 v) {
 static inline int node_is_leaf(const hiprz_node* n) { return (n->meta & HIPRZ_NODE_LEAF) != 0; }
 static inline uint32_t node_count(const hiprz_node* n) { return n->meta & HIPRZ_NODE_COUNT_MASK; }
 
+#ifdef RZ_MUT_LEAF_EIGHT
+static _Thread_local uint32_t mut_mesh_root; /* the root of the mesh tree being walked (closest_instance) */
+#endif
 /* closestIntersection(const Mesh&, ...) :331-352 */
 static void closest_mesh(const kctx* k, uint32_t node_idx, ray_t* ray, traversal_t* tr) {
     const hiprz_node* node = &k->s->nodes[node_idx];
     COUNT(k, box_tests, 1);
     if (!box_hit(node->bb_min, node->bb_max, ray)) return;
     if (node_is_leaf(node)) {
-        const uint32_t end = node->begin + node_count(node);
+        uint32_t end = node->begin + node_count(node);
+#ifdef RZ_MUT_LEAF_EIGHT /* mutant: the loop over a leaf below the mesh's root stops after 8 triangles */
+        if (node_idx != mut_mesh_root && node_count(node) > 8u) end = node->begin + 8u;
+#endif
         for (uint32_t i = node->begin; i < end; ++i) {
             float t, b1, b2, det;
             COUNT(k, tri_tests, 1);
-            if (tri_hit(&k->s->tris[i], ray, &t, &b1, &b2, &det)) {
-                ray->far_ = t;
-                tr->closest_triangle = (int32_t)i;
-                tr->external = det > 0.0f;
-                tr->bx = b1;
-                tr->by = b2;
-            }
+#ifdef RZ_MUT_TIE_LATER /* mutant: of two hits at equal t inside one leaf, the later wins when they are at least 8 positions apart */
+            if (tr->closest_triangle >= (int32_t)node->begin && i - (uint32_t)tr->closest_triangle >= 8u) {
+                ray_t wider = *ray;
+                wider.far_ = nextafterf(ray->far_, INFINITY);
+                if (!tri_hit(&k->s->tris[i], &wider, &t, &b1, &b2, &det)) continue;
+            } else
+#endif
+            if (!tri_hit(&k->s->tris[i], ray, &t, &b1, &b2, &det)) continue;
+            ray->far_ = t;
+            tr->closest_triangle = (int32_t)i;
+            tr->external = det > 0.0f;
+            tr->bx = b1;
+            tr->by = b2;
         }
     } else {
+#ifdef RZ_MUT_SIZE_SECOND /* mutant: the second child of a Size node (ptype 3) is skipped when the first child produced a hit */
+        const float far_before = ray->far_;
         closest_mesh(k, node->begin, ray, tr);
+        if ((node->meta >> HIPRZ_NODE_PTYPE_SHIFT & 3u) == 3u && ray->far_ != far_before) return;
+#else
+        closest_mesh(k, node->begin, ray, tr);
+#endif
         closest_mesh(k, node->begin + 1, ray, tr);
     }
 }
@@ -393,6 +411,9 @@ static void closest_instance(const kctx* k, uint32_t inst_idx, ray_t* ray, trave
     const int32_t closest_triangle = tr->closest_triangle;
     tr->closest_triangle = -1;
 
+#ifdef RZ_MUT_LEAF_EIGHT
+    mut_mesh_root = in->blas_root;
+#endif
     closest_mesh(k, in->blas_root, &local, tr);
     if (tr->closest_triangle >= 0) {
         tr->closest_instance = (int32_t)inst_idx;
@@ -614,7 +635,10 @@ static void any_mesh(const kctx* k, uint32_t node_idx, const ray_t* ray, float* 
     COUNT(k, shadow_box_tests, 1);
     if (!box_hit(node->bb_min, node->bb_max, ray)) return;
     if (node_is_leaf(node)) {
-        const uint32_t end = node->begin + node_count(node);
+        uint32_t end = node->begin + node_count(node);
+#ifdef RZ_MUT_SHADOW_SIXTYFOUR /* mutant: a shadow ray ignores the triangles from position 64 on in a leaf */
+        if (node_count(node) > 64u) end = node->begin + 64u;
+#endif
         for (uint32_t i = node->begin; i < end; ++i) {
             float t, b1, b2, det;
             COUNT(k, tri_tests, 1);
@@ -823,7 +847,10 @@ static float compat_emission(const kctx* k, const hiprz_material* m, float u, fl
  * return. */
 static int compat_mesh_node(const kctx* k, const hiprz_instance* in, const hiprz_node* node, const ray_t* ray, col* mask) {
     if (node_is_leaf(node)) {
-        const uint32_t end = node->begin + node_count(node);
+        uint32_t end = node->begin + node_count(node);
+#ifdef RZ_MUT_SHADOW_SIXTYFOUR /* the same mutant in the compat shadow walk */
+        if (node_count(node) > 64u) end = node->begin + 64u;
+#endif
         for (uint32_t i = node->begin; i < end; ++i) {
             const hiprz_tri* tri = &k->s->tris[i];
             float t, b1, b2, det;

@@ -512,6 +512,7 @@ __global__ void rz_build_world_tree_kernel(WorldViews w) {
 // most kSahSmall triangles runs the host's recursion on its own run of positions.  Boxes are then fitted exactly, bottom-up, by the refit kernel.
 // =======================================================================================
 constexpr uint32_t kSahBins = 16u, kSahLeaf = 8u, kSahSmall = 32u;
+constexpr uint32_t kSahRankMax = 8192u;  // largest halved node whose halves are chosen by triangle index (rz_sah_partition_kernel)
 constexpr float kSahTraversal = 4.0f;
 constexpr uint32_t kSahLarge = 1u, kSahSmallRoot = 2u, kSahLeafNode = 3u, kSahInner = 4u;  // node states (n_info & 7); axis in bits 4..5, plane in bits 8..12
 
@@ -714,7 +715,16 @@ __global__ void __launch_bounds__(256) rz_sah_partition_kernel(SahViews v, uint3
     uint32_t side = 0u, dest = p, child = node;
     if (moved) {
         const uint32_t axis = (info >> 4) & 3u, plane = (info >> 8) & 31u, first = v.n_first[node], count = v.n_count[node];
-        if (axis == 3u) side = (p - first) >= count / 2u ? 1u : 0u;
+        if (axis == 3u) {
+            // Halved: the lower half BY TRIANGLE INDEX, not by where the atomic cursors of the levels above happened to leave the
+            // triangle in the run, so the tree is a function of the mesh (the rank costs count reads: up to kSahRankMax triangles).
+            uint32_t rank = p - first;
+            if (count <= kSahRankMax) {
+                rank = 0u;
+                for (uint32_t k = 0u; k < count; ++k) rank += uint32_t(v.idx[cur][first + k] < t);
+            }
+            side = rank >= count / 2u ? 1u : 0u;
+        }
         else {
             const float* nb = v.n_box + 6 * size_t(node);
             const float ext = nb[3 + axis] - nb[axis];
@@ -749,8 +759,8 @@ __global__ void __launch_bounds__(64) rz_sah_small_kernel(SahViews v, uint32_t c
     {   // The top phase places triangles with per-wave atomic cursors: WHICH triangles a small root holds is decided by planes (deterministic),
         // the ORDER inside its run by wave scheduling.  The bottom phase reads that order twice (the two-pointer partition fixes the leaf
         // order; coincident centroids are cut "as the run stands"), so the run is put into triangle order first: the subtree is then a function
-        // of its triangle set, the same from run to run and on every device of a context.  (What stays order-dependent: a LARGE node whose
-        // centroids no plane separates is cut in half as its run stands — rz_sah_split_kernel; meshes with > 32 coincident centroids only.)
+        // of its triangle set, the same from run to run and on every device of a context.  (A LARGE node whose centroids no plane separates
+        // is cut in half by triangle index — rz_sah_partition_kernel — and "as its run stands" only above kSahRankMax coincident centroids.)
         const uint32_t first = v.n_first[stack[0]], count = v.n_count[stack[0]];
         for (uint32_t i = 1u; i < count; ++i) {
             const uint32_t t = idx[first + i];

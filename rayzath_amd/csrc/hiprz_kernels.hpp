@@ -937,7 +937,8 @@ __global__ void __launch_bounds__(256) rz_compat_pass_kernel(const DScene s, con
         Hit hit;
         hit.instance = -1, hit.triangle = 0u, hit.bx = hit.by = 0.0f, hit.external = true;
         int found = 0;
-        if (s.n_instances != 0u) found = closest_hit_skip<COUNT, false>(s, TopCache{nullptr, nullptr, 0u}, ps.ray, hit, cnt);
+        // TIES: this walk also runs on rebuilt and device-built trees, whose leaves hold the triangles in another order than the reference's
+        if (s.n_instances != 0u) found = closest_hit_skip<COUNT, false, true>(s, TopCache{nullptr, nullptr, 0u}, ps.ray, hit, cnt);
         if (scattered && found != 2) found = 3;
         shade_and_store<FIRST, COUNT, RZ_SHADOW_COMPAT>(s, cam, cfg, f, p, ps, found, hit, ShadowCtx{nullptr, TopCache{nullptr, nullptr, 0u}}, cnt, &rng);
     }

@@ -140,19 +140,30 @@ def bad(result):
 _STANDIN = {}
 
 
-def standin_counts(seed, mode=0, passes=None, names=STANDINS):
-    """{stand-in: lockstep result} of sweep scene `seed` with each libm stand-in in the device's place, against the plain oracle in
-    `mode`; computed once per (seed, mode, stand-in)."""
+def flat_scene(scene):
+    """(FlatScene, hiprz_camera, hiprz_config, World, RenderConfig) of a scene of either module: a name is one of
+    tests/tree_shape_scenes.py, anything else a seed (or a derived scene) of tests/generated_scenes.py"""
+    if isinstance(scene, str):
+        import tree_shape_scenes
+        return tree_shape_scenes.flat_scene(scene)
+    import generated_scenes
+    return generated_scenes.flat_scene(scene)
+
+
+def standin_counts(seed, mode=0, passes=None, names=STANDINS, threads=1):
+    """{stand-in: lockstep result} of sweep scene `seed` (or of the scene named `seed`, see flat_scene) with each libm stand-in in the
+    device's place, against the plain oracle in `mode`; computed once per (seed, mode, stand-in).  `threads` only shortens the wait:
+    the oracle's frames do not depend on it."""
     import generated_scenes
     passes = passes or generated_scenes.PASSES
-    flat, cam, cfg = generated_scenes.flat_scene(seed)[:3]
+    flat, cam, cfg = flat_scene(seed)[:3]
     out = {}
     for name in names:
         key = (seed, mode, passes, name)
         if key not in _STANDIN:
             dev = oracle.OracleRenderer(flat, cam, cfg, lib=oracle.variant(name), mode=mode)
             ref = oracle.OracleRenderer(flat, cam, cfg, mode=mode)
-            result = lockstep(OracleDevice(dev), ref, passes, records=0)
+            result = lockstep(OracleDevice(dev, threads=threads), ref, passes, records=0, threads=threads)
             dev.close(), ref.close()
             result.pop("depth", None)
             _STANDIN[key] = result
@@ -160,9 +171,9 @@ def standin_counts(seed, mode=0, passes=None, names=STANDINS):
     return out
 
 
-def scene_cap(seed, mode=0, passes=None):
+def scene_cap(seed, mode=0, passes=None, threads=1):
     """discrete + far segments a device may show on one scene: 2 x the largest count of a one-ulp stand-in, plus 2"""
-    return 2 * max(bad(r) for r in standin_counts(seed, mode, passes).values()) + 2
+    return 2 * max(bad(r) for r in standin_counts(seed, mode, passes, threads=threads).values()) + 2
 
 
 def sweep_cap(seeds, mode=0, passes=None):

@@ -6,8 +6,9 @@ Frames cannot see most tree mistakes — a tree decides what a ray meets, not wh
     clusters, copies of one triangle, the awkward meshes) passes tree_audit.audit: exact boxes, leaf sizes, tiling, the side rule;
   * every mesh of more than 4 triangles IS its reference tree (tree_reference.py: the builders restated in numpy float32) — the same
     triangle order, the same nodes, partition types and child order.  Left out of that comparison, and named here, are only the meshes
-    in AUDIT_ONLY_SAH under the SAH builder: a node of more than 32 coincident centres below the root is cut in half "as its run stands",
-    in an order that wave scheduling decides (rz_sah_split_kernel); they get the audit, which holds the halving rule and the leaf size.
+    in AUDIT_ONLY_SAH under the SAH builder: a node of more than 32 coincident centres below the root is cut in half, which the reference
+    marks as order-dependent (the device halves by triangle index, rz_sah_partition_kernel); they get the audit, which holds the halving
+    rule and the leaf size.
     ("40 copies" is halved at the root only, where the run still stands in triangle order: it is compared.)
   * hiprz_update_triangles over ranges that start inside one mesh and end inside a later one refits exactly the meshes it touches and
     keeps topology and order; hiprz_rebuild_trees builds the reference's tree over the order and the refitted box the device holds.
@@ -102,6 +103,27 @@ def test_first_build_is_the_reference_tree(built, device, devices):
     e = max(table, key=lambda e: e.n)
     assert tree_reference.differences(other[e.name], nodes, int(roots[e.instance]), refpos[e.first:e.first + e.n] - e.first, e.first)
     ctx.close()
+
+
+@pytest.mark.parametrize("devices", [0, [0, 0]])
+def test_halved_meshes_are_the_reference_tree_at_every_upload(built, devices):
+    """The meshes of AUDIT_ONLY_SAH under the SAH builder, in three fresh contexts: a node that no plane separates is halved by triangle
+    index, which is what tree_reference.sah_tree does (its `ix` ascends), so the device's tree IS the reference — the same triangle
+    order, nodes, partition types and child order — whatever the wave scheduling was."""
+    _, flat, table = sweep()
+    refs = sweep_references(tree_audit.SAH)
+    halved = [e for e in table if _audit_only(e, tree_audit.SAH)]
+    assert len(halved) >= 2 and all(refs[e.name].order_dependent for e in halved)
+    findings = []
+    for upload in range(3):
+        ctx = _upload(flat, DEVICE_SAH, devices)
+        nodes, roots, refpos = _download(ctx, flat)
+        ctx.close()
+        for e in halved:
+            mine = refpos[e.first:e.first + e.n]
+            assert sorted(mine.tolist()) == list(range(e.first, e.first + e.n)), e.name
+            findings += [f"upload {upload} {e.name}: {f}" for f in tree_reference.differences(refs[e.name], nodes, int(roots[e.instance]), mine - e.first, e.first)][:4]
+    assert not findings, "\n".join(findings[:40])
 
 
 def _update_ranges(table):

@@ -63,7 +63,7 @@ def _check_depth(result, seed, mode):
     if not mode & COMPAT_SCATTERING:
         assert result["depth_mismatch"] == 0, f"seed {seed}: first-hit depth differs on {result['depth_mismatch']} pixels"
         return
-    flat, cam, cfg = G.flat_scene(seed)[:3]
+    flat, cam, cfg = lockstep.flat_scene(seed)[:3]
     plain = oracle.OracleRenderer(flat, cam, cfg, mode=mode & ~COMPAT_SCATTERING)
     plain.render(1, threads=1)
     unscattered = rdepth == plain.depth

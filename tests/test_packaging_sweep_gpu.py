@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 import generated_scenes as G
+import lockstep
 import packaging_sweep as S
 from rayzath_amd.engine import Context
 from test_launch_plan import identity_line, kernel_identities, read_identities
@@ -36,7 +37,8 @@ CHUNK = 10
 SCENES = G.SEEDS + G.DERIVED                  # the sweep's 60 scenes, and the scenes without lights / without maps derived from them
 CHUNKS = [G.SEEDS[i:i + CHUNK] for i in range(0, len(G.SEEDS), CHUNK)] + [G.DERIVED]
 ENV = ("HIPRZ_BATCH_SEGMENTS", "HIPRZ_BATCH_WAVES", "HIPRZ_HEAVY_FIRST", "HIPRZ_TRACE_WAVES", "HIPRZ_SHADOW_PACKET", "HIPRZ_SHADOW_TREE",
-       "HIPRZ_SHADOW_SORT", "HIPRZ_DEFER_SHADOWS", "HIPRZ_SORT_BITS", "HIPRZ_NOLIGHT_KERNELS", "HIPRZ_WAVE_RESIDENT_MAX", "HIPRZ_SORT_KEY")
+       "HIPRZ_SHADOW_SORT", "HIPRZ_DEFER_SHADOWS", "HIPRZ_SORT_BITS", "HIPRZ_NOLIGHT_KERNELS", "HIPRZ_WAVE_RESIDENT_MAX", "HIPRZ_SORT_KEY",
+       "HIPRZ_WORLD_ADVANCE", "HIPRZ_WALK_ADVANCE")
 BASELINES = {"default": {}, "compat31": dict(mode=31)}   # lockstep's "default" and "compat31-split", rendered pass by pass
 OWN = "own"   # baseline of a variant that legitimately renders another frame: its own settings, rendered pass by pass (and in lockstep's CONFIGS)
 
@@ -143,8 +145,13 @@ def _context(spec, monkeypatch):
     return ctx
 
 
+def _scenes(chunk):
+    """a chunk of this file's sweep by its index, or a tuple of scenes as it stands (tests/test_tree_shapes_gpu.py)"""
+    return CHUNKS[chunk] if isinstance(chunk, int) else chunk
+
+
 def _upload(ctx, seed, config_seed=0):
-    flat, cam, cfg = G.flat_scene(seed)[:3]
+    flat, cam, cfg = lockstep.flat_scene(seed)[:3]
     if config_seed:
         cfg = type(cfg).from_buffer_copy(cfg)
         cfg.seed += config_seed
@@ -156,7 +163,7 @@ def baseline(name, chunk, monkeypatch):
     key = (name, chunk)
     if key not in _BASELINE:
         ctx, out = _context(_variant(**BASELINES[name]) if name in BASELINES else VARIANTS[name], monkeypatch), {}
-        for seed in CHUNKS[chunk]:
+        for seed in _scenes(chunk):
             _upload(ctx, seed)
             out[seed] = S.pass_by_pass(ctx)
             for snap in out[seed].values():
@@ -178,7 +185,7 @@ def run_chunk(name, chunk, monkeypatch, spec=None):
     want = baseline(name if spec["baseline"] == OWN else spec["baseline"], chunk, monkeypatch)
     start = time.perf_counter()
     ctx, out = _context(spec, monkeypatch), {}
-    for seed in CHUNKS[chunk]:
+    for seed in _scenes(chunk):
         _upload(ctx, seed, spec["config_seed"])
         diff = S.compare_patterns(ctx, want[seed])
         out[seed] = dict(differences=diff, identities=kernel_identities(ctx.launch_plan()))

@@ -130,7 +130,11 @@ def test_pairs_equal_the_stack_walk_and_the_oracle(name):
     root = int(flat.nodes[flat.tlas_root]["meta"])
     assert root & _abi.NODE_LEAF and (root & _abi.NODE_COUNT_MASK) == len(want_counts) <= 8
     assert sorted(leaf_counts(flat)) == sorted(want_counts)
-    cfg = RenderConfig(tracing=Tracing(6, 8)).struct()
+    compare_with_the_stack_walk(name, flat, cam, RenderConfig(tracing=Tracing(6, 8)).struct())
+
+
+def compare_with_the_stack_walk(name, flat, cam, cfg):
+    """the comparison of this file on one uploaded scene (tests/test_tree_shapes_gpu.py runs it on meshes of one leaf above 32 triangles)"""
     contexts = {}
     for label, mode, pipeline in (("stack walk", 1, None), ("pipeline 2", None, 2), ("pipeline 0", None, 0), ("pipeline 1", None, 1)):
         ctx = Context(0)

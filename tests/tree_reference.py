@@ -29,8 +29,8 @@ class RefNode:
 class RefTree:
     def __init__(self, order, root, order_dependent=False):
         self.order, self.root = np.asarray(order, dtype=np.int64), root
-        self.order_dependent = order_dependent   # a node of more than 32 coincident centres below the root was halved: the device cuts it as its
-                                                 # run stands, in an order that wave scheduling decides
+        self.order_dependent = order_dependent   # a node of more than 32 coincident centres below the root was halved: here by triangle index
+                                                 # (`ix` ascends), as the device does for up to 8 192 triangles; beyond that it cuts the run as it stands
 
     def walk(self):
         stack = [self.root]
