@@ -184,6 +184,30 @@ __global__ void __launch_bounds__(256) rz_selftest_div_kernel(uint32_t n_per_thr
                     __float_as_uint(best.b2) != __float_as_uint(seq_b2) || best.external != seq_external)
                     bad += 1;
             }
+            // tri_hit2's two reciprocals as one sequence (rcp_pair, RZ_FLAT_PK_DIV) against `1.0f / x`, bit for bit (a NaN for a NaN).  Called
+            // directly, whichever way the switch stands.  By the bits of `sel`: any bit pattern at all; a determinant the nudge has
+            // lifted (0 < x < 2e-7) or one just outside it; an x whose reciprocal is denormal or rounds to the largest finite values
+            // (|x| >= 2^126); a denormal or tiny x (the reciprocal overflows or nearly does); +-0, +-inf and NaNs.
+            {
+                auto operand = [&](uint32_t k) {
+                    const uint32_t w = mix32(h + 0x51EDu * k), sel = (w >> 3) & 7u, sign = w & 0x80000000u, frac = mix32(w) & 0x7FFFFFu;
+                    if (sel == 0u) return __uint_as_float(mix32(w ^ 0x3C6EF372u));
+                    if (sel == 1u) return unit(50u + k) * 2.0e-7f;
+                    if (sel == 2u) return __uint_as_float(sign | __float_as_uint(1.0e-7f + (unit(52u + k) - 0.5f) * 1.0e-9f));
+                    if (sel == 3u) return __uint_as_float(sign | ((253u + (w >> 8) % 2u) << 23) | frac);
+                    if (sel == 4u) return __uint_as_float(sign | (((w >> 8) % 3u) << 23) | frac);
+                    if (sel == 5u) {
+                        const uint32_t special[4] = {0x00000000u, 0x7F800000u, 0x7FC00000u | frac, 0x7F800001u};
+                        return __uint_as_float(sign | special[(w >> 8) & 3u]);
+                    }
+                    return __uint_as_float(sign | ((64u + (w >> 8) % 128u) << 23) | frac);  // ordinary magnitudes, 2^-63 .. 2^64
+                };
+                const f2 x = {operand(1u), operand(2u)};
+                const f2 got = rcp_pair(x);
+                const float want_x = 1.0f / x.x, want_y = 1.0f / x.y;
+                if (__float_as_uint(got.x) != __float_as_uint(want_x) && !(got.x != got.x && want_x != want_x)) bad += 1;
+                if (__float_as_uint(got.y) != __float_as_uint(want_y) && !(got.y != got.y && want_y != want_y)) bad += 1;
+            }
         }
     }
     atomicAdd(&out[0], (unsigned long long)bad);

@@ -38,6 +38,12 @@ namespace hiprz {
 #ifndef RZ_FLAT_PAIR_TRIS      // one-leaf walk: the triangles of a leaf tested two at a time on float2 vectors (tri_hit2)
 #define RZ_FLAT_PAIR_TRIS 1    // on: +3.9 % on config B measured alone
 #endif
+#ifndef RZ_FLAT_PAIR_RECORDS   // ... read from pair records (the two triangles interleaved: one address, loads in operand order) instead of two 48-byte records
+#define RZ_FLAT_PAIR_RECORDS 1 // on: +2.7 % on config B measured alone (profiles/r14)
+#endif
+#ifndef RZ_FLAT_PK_DIV         // ... and tri_hit2's two true divisions as ONE sequence, its six plain operations packed (rcp_pair)
+#define RZ_FLAT_PK_DIV 0       // off: on top of the records it takes 0.5 % back, alone the five-wave build spills inside the walk (-17.7 %)
+#endif
 #ifndef RZ_TRACE_MIN_WAVES
 #define RZ_TRACE_MIN_WAVES 5
 #endif
@@ -93,7 +99,9 @@ struct DScene {
     uint32_t fast_div;  // every node / instance box coordinate is 0 or in [2^-60, 2^40): shared-reciprocal division is exact
     // The geometry + shading records live in ONE device buffer ("hot blob": nodes | tlas_order |
     // instances | tris | tri_attrs | materials | inst_materials, each section 16-B aligned) so a
-    // workgroup can stage it into LDS with one strided copy when it is small enough.
+    // workgroup can stage it into LDS with one strided copy when it is small enough.  Behind the blob, in the same buffer and
+    // counted in hot_bytes: the pair records of the single-leaf meshes of a one-leaf world (hiprz_scene_host.hpp: pair_section),
+    // 0 bytes for every other scene.
     uint32_t hot_bytes;
     const float4* hot;  // start of the blob
     uint32_t off_nodes, off_tlas_order, off_instances, off_tris, off_tri_attrs, off_materials, off_inst_materials;
@@ -107,6 +115,10 @@ struct DScene {
     uint32_t walk_advance;         // cooperative walks: further instance boxes a lane may test in one round while it has found none to enter
     uint32_t world_advance;        // ... and further world-tree nodes a lane may step through while it holds no leaf
     uint32_t walk_h;               // cooperative walks: the node phase of a round ends as soon as this many lanes hold a leaf
+    // Where the pair section starts in the hot buffer (= the blob's size).  The word fills what was padding in front of the pointer
+    // below: no other field moves, so the kernels that never read it keep their arguments and their code byte for byte.  There is no
+    // pointer field for the same reason — pair_section() derives it from `nodes`, which repoint_hot has pointed at the staged copy.
+    uint32_t off_pairs;
     // front-to-back mesh walk (hiprz_set_walk_order): 64-B records = node (32 B) + its skip link under each of the 8
     // ray-direction octants
     const float4* nodes64;
@@ -129,6 +141,12 @@ RZ_DEV void repoint_hot(DScene& v, const unsigned char* base) {
     v.materials = reinterpret_cast<const float4*>(base + v.off_materials);
     v.inst_materials = reinterpret_cast<const int32_t*>(base + v.off_inst_materials);
 }
+
+// The pair section of a scene staged in LDS (only those are walked by the code that reads it: the snapshot's own trees, nodes inside
+// the hot buffer): a 16-bit table instance id -> start of its mesh's first pair record in units of 8 bytes from the section's start,
+// then the records (hiprz_scene_host.hpp: PackedScene::pair_section).
+static_assert(sizeof(DScene) == 256, "off_pairs fills a padding word: the kernels' argument layout is what it was");
+RZ_DEV const unsigned char* pair_section(const DScene& s) { return reinterpret_cast<const unsigned char*>(s.nodes) - s.off_nodes + s.off_pairs; }
 
 struct DCamera {
     float position[3];
@@ -599,13 +617,36 @@ struct v3p {
     f2 x, y, z;
 };
 RZ_DEV v3p pair3(float4 a, float4 b) { return v3p{f2{a.x, b.x}, f2{a.y, b.y}, f2{a.z, b.z}}; }
+// {1.0f / x.x, 1.0f / x.y}: the compiler's own expansion of the correctly rounded `1.0f / x`, operation for operation and in its order —
+// v_div_scale twice, v_rcp, six fused or plain operations, v_div_fmas, v_div_fixup — with the six in the middle, which are plain IEEE
+// operations, on both elements at once.  Nothing is removed or reordered: this is not a shorter division.  hiprz_selftest compares it
+// with `/` bit for bit.
+RZ_DEV f2 rcp_pair(f2 x) {
+    bool scaled_x, scaled_y, unused;
+    const f2 den = {__builtin_amdgcn_div_scalef(1.0f, x.x, false, &unused), __builtin_amdgcn_div_scalef(1.0f, x.y, false, &unused)};
+    const f2 num = {__builtin_amdgcn_div_scalef(1.0f, x.x, true, &scaled_x), __builtin_amdgcn_div_scalef(1.0f, x.y, true, &scaled_y)};
+    const f2 rcp = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+    const f2 nden = -den, one = {1.0f, 1.0f};
+    const f2 e0 = __builtin_elementwise_fma(nden, rcp, one);
+    const f2 r1 = __builtin_elementwise_fma(e0, rcp, rcp);
+    const f2 q0 = num * r1;
+    const f2 e1 = __builtin_elementwise_fma(nden, q0, num);
+    const f2 q1 = __builtin_elementwise_fma(e1, r1, q0);
+    const f2 e2 = __builtin_elementwise_fma(nden, q1, num);
+    return f2{__builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e2.x, r1.x, q1.x, scaled_x), x.x, 1.0f),
+              __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e2.y, r1.y, q1.y, scaled_y), x.y, 1.0f)};
+}
 RZ_DEV float det_nudge(float det) { return float(uint32_t(det > -1.0e-7f) & uint32_t(det < 1.0e-7f)) * 1.0e-7f; }
 RZ_DEV void tri_hit2(v3p v1, v3p edge1, v3p edge2, const WalkRay& r, bool& inside_a, bool& inside_b, f2& t_out, f2& b1_out, f2& b2_out, f2& det_out) {
     const f2 dx = {r.d.x, r.d.x}, dy = {r.d.y, r.d.y}, dz = {r.d.z, r.d.z};
     const v3p pvec = {dy * edge2.z - dz * edge2.y, dz * edge2.x - dx * edge2.z, dx * edge2.y - dy * edge2.x};
     f2 det = edge1.x * pvec.x + edge1.y * pvec.y + edge1.z * pvec.z;
     det = det + f2{det_nudge(det.x), det_nudge(det.y)};
+#if RZ_FLAT_PK_DIV
+    const f2 inv_det = rcp_pair(det);
+#else
     const f2 inv_det = {1.0f / det.x, 1.0f / det.y};
+#endif
     const v3p tvec = {f2{r.o.x, r.o.x} - v1.x, f2{r.o.y, r.o.y} - v1.y, f2{r.o.z, r.o.z} - v1.z};
     const f2 b1 = (tvec.x * pvec.x + tvec.y * pvec.y + tvec.z * pvec.z) * inv_det;
     const v3p qvec = {tvec.y * edge1.z - tvec.z * edge1.y, tvec.z * edge1.x - tvec.x * edge1.z, tvec.x * edge1.y - tvec.y * edge1.x};
@@ -636,6 +677,21 @@ RZ_DEV void tri_pair_step(float4 a0, float4 a1, float4 a2, float4 b0, float4 b1,
     if (pick.winner != 0u) {
         const bool second = pick.winner == 2u;
         best.triangle = second ? ib : ia;
+        best.b1 = second ? u.y : u.x, best.b2 = second ? v.y : v.x;
+        best.external = (second ? det.y : det.x) > 0.0f;
+    }
+}
+// ... on a pair record's operands: triangles ia and ia + 1.  (A function of its own, and the one above left as it was: routed through
+// this one, the loop on 48-byte records came out of the compiler with four selects in another order.)
+RZ_DEV void tri_pair_step(v3p v1, v3p edge1, v3p edge2, uint32_t ia, bool has_b, const WalkRay& r, LeafBest& best) {
+    f2 t, u, v, det;
+    bool inside_a, inside_b;
+    tri_hit2(v1, edge1, edge2, r, inside_a, inside_b, t, u, v, det);
+    const PairPick pick = pair_pick(inside_a, inside_b && has_b, t.x, t.y, best.far_);
+    best.far_ = pick.far_;
+    if (pick.winner != 0u) {
+        const bool second = pick.winner == 2u;
+        best.triangle = second ? ia + 1u : ia;
         best.b1 = second ? u.y : u.x, best.b2 = second ? v.y : v.x;
         best.external = (second ? det.y : det.x) > 0.0f;
     }
@@ -966,6 +1022,27 @@ RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_c
         best.far_ = lr.far_, best.triangle = 0xFFFFFFFFu, best.b1 = best.b2 = 0.0f, best.external = false;
         if (box_hit_packed<RCP>(n0, n1, lr)) {
             const uint32_t begin = __float_as_uint(n1.z), end = begin + (__float_as_uint(n1.w) & HIPRZ_NODE_COUNT_MASK);
+#if RZ_FLAT_PAIR_RECORDS
+            // Pair record p of the leaf holds its triangles 2p and 2p + 1, interleaved: one address, nine 8-byte values in five reads,
+            // and the registers are tri_hit2's operands as they arrive.  A lane on its own takes p = 0, 1, ...; lane j of an octet p = j,
+            // j + 8, ... — it pairs (i, i + 1) like a lone lane (a 12-triangle cube is one trip of lanes 0..5).  A lane's pairs still follow
+            // one another in leaf order, and octet_min below merges on (distance, triangle): the nearest hit, the first in leaf order among
+            // equals, whatever the partition.  The b half of an odd leaf's last record repeats a and is masked by has_b.
+            const uint32_t count = end - begin, n_pairs = (count + 1u) >> 1;
+            const unsigned char* section = pair_section(s);
+            const float2* rec = reinterpret_cast<const float2*>(section + 8u * reinterpret_cast<const uint16_t*>(section)[inst]);
+            for (uint32_t p = j; p < n_pairs; p += wide ? 8u : 1u) {
+                const float2* q = rec + p * (RZ_PAIR_RECORD_BYTES / 8u);
+                const float2 v1x = q[0], v1y = q[1], v1z = q[2], e1x = q[3], e1y = q[4], e1z = q[5], e2x = q[6], e2y = q[7], e2z = q[8];
+                const bool has_b = 2u * p + 1u < count;
+                const uint32_t i = begin + 2u * p;
+                RZ_PHASE(4);
+                if constexpr (COUNT) cnt.tri_tests += has_b ? 2u : 1u;
+                tri_pair_step(v3p{f2{v1x.x, v1x.y}, f2{v1y.x, v1y.y}, f2{v1z.x, v1z.y}}, v3p{f2{e1x.x, e1x.y}, f2{e1y.x, e1y.y}, f2{e1z.x, e1z.y}},
+                              v3p{f2{e2x.x, e2x.y}, f2{e2y.x, e2y.y}, f2{e2z.x, e2z.y}}, i, has_b, lr, best);
+            }
+            (void)partner;
+#else
             for (uint32_t i = begin + j; i < end; i += 2u * partner) {
                 const bool has_b = i + partner < end;
                 const uint32_t ib = has_b ? i + partner : i;  // (a lone triangle is loaded twice: no record past the leaf is touched)
@@ -975,6 +1052,7 @@ RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_c
                 if constexpr (COUNT) cnt.tri_tests += has_b ? 2u : 1u;
                 tri_pair_step(a0, a1, a2, b0, b1, b2, i, ib, has_b, lr, best);
             }
+#endif
         }
         bool mine = best.triangle != 0xFFFFFFFFu;
         if (wide) {

@@ -121,7 +121,14 @@ int build_shadow_world_tree(hiprz_ctx* c, const std::vector<hiprz_instance>& din
 // every copy of the upload, on the context's stream; synchronous on return (host staging and the caller's arrays may go away)
 int copy_scene(hiprz_ctx* c, const hiprz_scene& sc, const PackedScene& packed, bool device_trees) {
     (void)hipSetDevice(c->device);
-    RZ_HIP(c, c->hot.assign(packed.blob.data(), packed.blob.size(), c->stream));
+    if (packed.pair_section.empty()) {
+        RZ_HIP(c, c->hot.assign(packed.blob.data(), packed.blob.size(), c->stream));
+    } else {  // the pair records stand directly behind the blob: one hot buffer, staged as a whole (DScene::hot_bytes is the total)
+        std::vector<uint8_t> hot(packed.blob);
+        hot.insert(hot.end(), packed.pair_section.begin(), packed.pair_section.end());
+        RZ_HIP(c, c->hot.assign(hot.data(), hot.size(), c->stream));
+        RZ_HIP(c, hipStreamSynchronize(c->stream));  // (`hot` goes away)
+    }
     RZ_HIP(c, c->node_skip.assign(packed.skip.data(), packed.skip.size(), c->stream));
     if (device_trees) {  // the node records of the whole scene in a buffer of their own: the uploaded prefix + room for what the device builds
         hiprz_node unused{};
@@ -170,7 +177,8 @@ void bind_scene(hiprz_ctx* c, const ChosenTrees& trees, const PackedScene& packe
     d.mesh_stack_entries = chk.mesh_depth + 1u;
     d.off_nodes = packed.off_nodes, d.off_tlas_order = packed.off_tlas_order, d.off_instances = packed.off_instances, d.off_tris = packed.off_tris;
     d.off_tri_attrs = packed.off_tri_attrs, d.off_materials = packed.off_materials, d.off_inst_materials = packed.off_inst_materials;
-    d.hot_bytes = uint32_t(packed.blob.size());
+    d.off_pairs = uint32_t(packed.blob.size());
+    d.hot_bytes = uint32_t(packed.hot_bytes());
     d.hot = reinterpret_cast<const float4*>(c->hot.ptr);
     d.nodes = reinterpret_cast<const float4*>(trees.device_trees() ? c->dev_nodes.ptr : c->hot.ptr + d.off_nodes);
     d.tlas_order = reinterpret_cast<const uint32_t*>(c->hot.ptr + d.off_tlas_order);

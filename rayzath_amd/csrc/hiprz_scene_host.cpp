@@ -286,7 +286,7 @@ int choose_trees(const hiprz_scene* sc, uint32_t tree_mode, size_t lds_limit, Sc
     return HIPRZ_OK;
 }
 
-int pack_scene(const ChosenTrees& trees, DerivedTables&& derived, PackedScene& out, std::string& error) {
+int pack_scene(const ChosenTrees& trees, DerivedTables&& derived, PackedScene& out, std::string& error, bool pair_records) {
     const hiprz_scene* sc = &trees.scene;
     out.new_index = std::move(derived.new_index), out.nodes = std::move(derived.dnodes), out.skip = std::move(derived.dskip);
     const std::vector<uint32_t>& new_index = out.new_index;
@@ -379,6 +379,47 @@ int pack_scene(const ChosenTrees& trees, DerivedTables&& derived, PackedScene& o
         out.bounds_scale[a] = hi > lo ? 32.0f / (hi - lo) : 0.0f;
     }
     out.flat_world = sc->n_instances != 0u && (sc->nodes[sc->tlas_root].meta & HIPRZ_NODE_LEAF) && (sc->nodes[sc->tlas_root].meta & HIPRZ_NODE_COUNT_MASK) <= 8u;
+    // the pair records of the single-leaf meshes (hiprz_scene_host.hpp: PackedScene::pair_section), copied from the blob's triangle records
+    out.pair_section.clear();
+    if (pair_records && out.flat_world && !trees.own_trees) {
+        const uint32_t table_bytes = ((sc->n_instances + 3u) & ~3u) * 2u;
+        std::vector<uint16_t> table(table_bytes / 2u, kPairNone);
+        std::vector<uint32_t> first_of_root(sc->n_nodes, RZ_END);
+        std::vector<uint8_t> records;
+        bool any = false;
+        for (uint32_t i = 0; i < sc->n_instances; ++i) {
+            const uint32_t root = sc->instances[i].blas_root;
+            if (root >= sc->n_nodes || !(sc->nodes[root].meta & HIPRZ_NODE_LEAF)) continue;
+            if (first_of_root[root] == RZ_END) {
+                first_of_root[root] = (table_bytes + uint32_t(records.size())) / 8u;
+                const uint32_t begin = sc->nodes[root].begin, n = sc->nodes[root].meta & HIPRZ_NODE_COUNT_MASK;
+                for (uint32_t p = 0; 2u * p < n && records.size() < kPairSectionLimit; ++p) {
+                    hiprz_tri ab[2];
+                    std::memcpy(&ab[0], blob.data() + out.off_tris + sizeof(hiprz_tri) * (begin + 2u * p), sizeof(hiprz_tri));
+                    ab[1] = ab[0];  // an odd leaf's last record repeats a in b
+                    if (2u * p + 1u < n) std::memcpy(&ab[1], blob.data() + out.off_tris + sizeof(hiprz_tri) * (begin + 2u * p + 1u), sizeof(hiprz_tri));
+                    float rec[kPairRecordBytes / 4u];
+                    for (int k = 0; k < 3; ++k)
+                        for (int e = 0; e < 2; ++e) rec[2 * k + e] = ab[e].v1[k], rec[6 + 2 * k + e] = ab[e].v2[k], rec[12 + 2 * k + e] = ab[e].v3[k];
+                    const size_t at = records.size();
+                    records.resize(at + kPairRecordBytes);
+                    std::memcpy(records.data() + at, rec, kPairRecordBytes);
+                }
+            }
+            table[i] = uint16_t(first_of_root[root]), any = true;
+        }
+        // (beyond the limit a table entry could not say where a mesh's records start: no section — the blob of such a scene, 144 bytes
+        // per triangle against the section's 36, is far beyond what any kernel stages in LDS, and only staged scenes are read through it)
+        if (any && table_bytes + records.size() <= kPairSectionLimit) {
+            out.pair_section.assign((table_bytes + records.size() + 15u) & ~size_t(15), 0);
+            std::memcpy(out.pair_section.data(), table.data(), table_bytes);
+            if (!records.empty()) std::memcpy(out.pair_section.data() + table_bytes, records.data(), records.size());
+        }
+        if (out.hot_bytes() > 0xFFFFFFF0ull) {
+            error = "scene geometry exceeds 4 GiB";
+            return HIPRZ_ERR_INVALID;
+        }
+    }
     std::vector<uint8_t> member(sc->n_instances ? sc->n_instances : 1u, 0);
     for (uint32_t k = 0; k < sc->n_tlas_order; ++k)
         if (sc->tlas_order[k] < sc->n_instances) member[sc->tlas_order[k]] = 1;

@@ -15,6 +15,9 @@
 namespace hiprz {
 
 constexpr uint32_t kLeafMax = 4u;  // device-built mesh trees: one quad entry of the cooperative triangle phase (hiprz_build.hip)
+constexpr uint32_t kPairRecordBytes = RZ_PAIR_RECORD_BYTES;  // two triangles of a single-leaf mesh, interleaved (PackedScene::pair_section)
+constexpr uint16_t kPairNone = 0xFFFFu;                       // table entry of an instance whose mesh has no pair record
+constexpr size_t kPairSectionLimit = 8u * 0xFFFEu;            // what a 16-bit table entry in units of 8 bytes can address
 
 // one mesh of a scene whose trees are built on the device (hiprz_build.hip)
 struct DeviceMesh {
@@ -129,6 +132,22 @@ struct PackedScene {
     float bounds_min[3] = {0, 0, 0}, bounds_scale[3] = {0, 0, 0};  // the world root's box, 32 cells per axis
     uint32_t tlas_root = 0;
     bool flat_world = false;                  // the world tree is one leaf of at most 8 instances
+    // Pair records: what the one-leaf walk's triangle loop reads (hiprz_device.hpp: binned_visit, RZ_FLAT_PAIR_RECORDS).  NOT part of
+    // `blob`: the upload places the section directly behind the blob in the device's hot buffer, and DScene::hot_bytes is the total,
+    // so whatever stages or sizes the hot buffer carries the section along.  Empty unless the world is flat, the snapshot's own trees
+    // are walked and some instance's mesh is ONE leaf.  Layout: a table of ((n_instances + 3) & ~3) 16-bit words — instance id -> where
+    // its mesh's first pair record starts, in units of 8 bytes from the section's start, kPairNone for a mesh that is not one leaf
+    // (instances of one mesh share records) —, then per such mesh ceil(n / 2) records of kPairRecordBytes, 8-byte aligned: nine float2
+    // {a, b} = v1.x, v1.y, v1.z, edge1.x .. edge2.z of triangles begin + 2p (a) and begin + 2p + 1 (b) of the leaf, bit copies of the
+    // blob's triangle records; the last record of an odd leaf repeats a in b.  Zeros pad the section to a multiple of 16 bytes.
+    // Why as small as this (no padding to 80-byte records, no 32-bit table): config B's five workgroups per CU have 592 bytes of LDS to
+    // spare below 25 allocation blocks of 1 280 bytes each — its eight records and eight table entries are 592 bytes; at 672 bytes the
+    // fifth workgroup no longer fits and the kernel loses 5 %.
+    // The section cannot go stale: only scenes with the snapshot's trees are ever staged in LDS (hiprz_plan.cpp: use_lds_scene), and
+    // hiprz_update_triangles / hiprz_rebuild_trees require HIPRZ_TREE_DEVICE — the triangles of a scene that has a section change
+    // through hiprz_upload_scene alone, which packs again.
+    std::vector<uint8_t> pair_section;
+    size_t hot_bytes() const { return blob.size() + pair_section.size(); }  // what the device's hot buffer holds
     // device-built trees (ChosenTrees::device_trees): room behind the uploaded prefix for the world tree (2 * instances + 1 slots) and
     // for every mesh tree (2 * triangles - 1 slots); regions start at odd slots, their child pairs at even ones
     std::vector<DeviceMesh> device_meshes;
@@ -136,7 +155,8 @@ struct PackedScene {
     uint32_t world_region = 0, node_capacity = 0;
 };
 // From a validated snapshot (`trees.scene` passed check_scene, `derived` are its tables, consumed).  HIPRZ_ERR_INVALID + `error`.
-int pack_scene(const ChosenTrees& trees, DerivedTables&& derived, PackedScene& out, std::string& error);
+// `pair_records` = false leaves pair_section empty and everything else what it is with it (tests/test_pair_records.py compares the two).
+int pack_scene(const ChosenTrees& trees, DerivedTables&& derived, PackedScene& out, std::string& error, bool pair_records = true);
 
 // Instances enter their mesh at the root the device built (where it built one); returns the nodes the builds emitted.
 uint32_t enter_device_roots(std::vector<hiprz_instance>& instances, const std::vector<uint32_t>& instance_mesh, const std::vector<DeviceMesh>& meshes,
