@@ -666,6 +666,12 @@ int hiprz_set_variance(hiprz_ctx* ctx, int enabled);                      /* def
 int hiprz_read_variance(hiprz_ctx* ctx, float* dst, size_t bytes);
 /* The same image on the head device, enqueued on the context's stream: the contract of hiprz_guides_device. */
 int hiprz_variance_device(hiprz_ctx* ctx, const void** out);
+/* The selected camera's accumulator as hiprz_read_accum defines it — row-major W*H float4 on the head device, all parts assembled, summed
+ * under HIPRZ_SHARD_SAMPLES — enqueued on the context's stream: the contract of hiprz_variance_device, with one addition.  The image lives
+ * in the staging every readback shares: it is valid only until the next call on this context that reads back (hiprz_read_*), denoises
+ * (hiprz_denoise) or presents (hiprz_present).  Host only: no kernel of its own.  HIPRZ_ERR_STATE before scene and camera upload,
+ * HIPRZ_ERR_INVALID on a null output.  Beside hiprz_variance_device it feeds the noise meter of include/hiprz_noise.h. */
+int hiprz_accum_device(hiprz_ctx* ctx, const void** out);
 
 /* Device self-test of the kernels' exact-arithmetic shortcuts (shared-reciprocal division must
  * equal the correctly rounded quotient): runs 262144 * cases_per_thread random cases. */

@@ -199,6 +199,7 @@ ENTRY_POINTS = {
     "hiprz_set_variance": (C.c_int, [P, C.c_int]),
     "hiprz_read_variance": (C.c_int, [P, P, SZ]),
     "hiprz_variance_device": (C.c_int, [P, C.POINTER(P)]),
+    "hiprz_accum_device": (C.c_int, [P, C.POINTER(P)]),
     "hiprz_denoise_layout": (None, [P]),
     "hiprz_selftest": (C.c_int, [P, U32, U32, C.POINTER(U64), C.POINTER(U64)]),
     "hiprz_selftest_sort": (C.c_int, [P, C.POINTER(U32), U32, C.c_int, U32, C.POINTER(U64), C.POINTER(C.c_double)]),

@@ -86,6 +86,10 @@ std::vector<RenderTask> prepareTasks(const std::string& task_file) {
                 else if (!v->is_bool()) throw std::runtime_error("denoise key must be true, false or \"variance\"");
                 else t.denoise = v->b;
             }
+            if (const IO::Json* v = e.find("noise")) {
+                if (!v->is_number() || !(v->num > 0.0) || !std::isfinite(v->num)) throw std::runtime_error("noise key must be a positive number (the target in display units)");
+                t.noise = float(v->num);
+            }
             return t;
         };
         std::vector<RenderTask> tasks;
@@ -136,6 +140,15 @@ std::vector<TaskResult> executeTask(const RenderTask& task, const std::string& r
             params.flags |= HIPRZ_DENOISE_VARIANCE, params.sigma_color = 4.0f;
             engine.setDenoise(&params);
         }
+        const bool to_target = task.noise > 0.0f;
+        if (to_target) engine.setMeasuring(true);  // likewise: on from the first call
+        const uint32_t min_batches = 8;
+        hiprz_noise_summary noise{};
+        bool noise_met = false;
+        auto rule = [&]() {
+            engine.noise(noise, 1.0f / 255.0f, min_batches);
+            return noise.estimated == noise.pixels && noise.tile_rms_max <= double(task.noise);
+        };
         const float load_time = 0.1f;
         float floaty_rpp = 1.0f;
         auto render = [&]() {
@@ -153,6 +166,7 @@ std::vector<TaskResult> executeTask(const RenderTask& task, const std::string& r
         render();  // warm-up (headless.cpp:203)
         const auto start = clock_t_::now();
         auto last_stop = start;
+        uint32_t calls = 1;  // the warm-up was a batch too
         for (traced = 0; traced < task.rpp;) {
             if (task.rpp - traced < config.tracing.rpp) config.tracing.rpp = task.rpp - traced;
             const uint32_t this_call = config.tracing.rpp;
@@ -169,6 +183,7 @@ std::vector<TaskResult> executeTask(const RenderTask& task, const std::string& r
                 std::printf("\rRendering... %u/%u +%u [rpp] (%.2f%%) | %s rps | %.3fs (timeout: %.3fs)   ", traced, task.rpp, config.tracing.rpp,
                             traced / float(task.rpp) * 100.0f, scientificWithPrefix(size_t(diff / pass_duration)).c_str(), task_duration, task.timeout);
             if (task_duration >= task.timeout) break;
+            if (to_target && ++calls >= min_batches && (noise_met = rule())) break;  // (the measurement waits for the stream: such tasks trade overlap for the answer)
         }
         // the calls above are pipelined (sync = false): one more pass with sync = true puts the final frame into the camera
         // buffers, and the clock stops when it is there
@@ -181,6 +196,13 @@ std::vector<TaskResult> executeTask(const RenderTask& task, const std::string& r
         engine.renderWorld(world, config, true, true);
         result.total_traced_rays += size_t(world.camera.width) * world.camera.height * rays_per_pass_scale;
         result.duration = seconds_since(start);
+        if (to_target) {  // the figures of the frame that is kept
+            const bool met_now = rule();
+            result.noise_target = task.noise, result.noise_met = noise_met || met_now;
+            result.noise_tile_rms_max = noise.tile_rms_max, result.noise_rms = noise.rms;
+            result.noise_estimated_share = noise.pixels ? double(noise.estimated) / double(noise.pixels) : 0.0;
+            result.noise_passes = traced + 1u;
+        }
         if (!quiet) std::printf("\nRendered in: %ss\n\n", fixed3(result.duration).c_str());
         if (save_images) {
             // saveMap<Texture> (headless.cpp:255-275, saver.cpp:16-37): the camera's RGBA8 frame as a PNG
@@ -202,6 +224,12 @@ std::string reportText(const std::vector<TaskResult>& results) {
         out += "\tengine: " + r.engine + " | max depth: " + std::to_string(r.max_depth) + "\n";
         out += "\tduration: " + fixed3(r.duration) + "s | traced " + scientificWithPrefix(r.total_traced_rays) + " rays (" +
                scientificWithPrefix(r.duration > 0 ? size_t(r.total_traced_rays / r.duration) : 0) + " rps)\n";
+        if (r.noise_target > 0.0f) {
+            char line[256];
+            std::snprintf(line, sizeof line, "\tnoise: tile rms max %.5f | rms %.5f | estimated %.1f%% | target %.5f %s | %u passes\n", r.noise_tile_rms_max, r.noise_rms,
+                          100.0 * r.noise_estimated_share, double(r.noise_target), r.noise_met ? "met" : "not met", r.noise_passes);
+            out += line;
+        }
     }
     return out;
 }

@@ -339,12 +339,15 @@ Engine::Engine(int device, int streams) : m_device(device) {
     if (rc != HIPRZ_OK) throw Exception(rc, std::string("HIPGPU backend unavailable: ") + hiprz_last_error(nullptr));
     check(hiprz_set_tree(m_ctx, m_tree));
 }
-Engine::Engine(const std::vector<int>& devices) {
+Engine::Engine(const std::vector<int>& devices) : m_device(devices.empty() ? 0 : devices[0]) {
     const int rc = hiprz_create_multi(&m_ctx, devices.data(), int(devices.size()));
     if (rc != HIPRZ_OK) throw Exception(rc, std::string("HIPGPU backend unavailable: ") + hiprz_last_error(nullptr));
     check(hiprz_set_tree(m_ctx, m_tree));
 }
-Engine::~Engine() { hiprz_destroy(m_ctx); }
+Engine::~Engine() {
+    if (m_meter) hiprz_noise_destroy(m_meter);
+    hiprz_destroy(m_ctx);
+}
 
 void Engine::check(int rc) {
     if (rc != HIPRZ_OK) throw Exception(rc, hiprz_last_error(m_ctx));
@@ -361,11 +364,56 @@ void Engine::shardMode(ShardMode mode) {
 }
 void Engine::setDenoise(const hiprz_denoise_params* params) {
     std::lock_guard<std::mutex> lock(m_mutex);
-    // the context's variance estimate is on exactly while the parameters ask for the variance-guided filter (a change restarts accumulation)
-    check(hiprz_set_variance(m_ctx, params && (params->flags & HIPRZ_DENOISE_VARIANCE) ? 1 : 0));
+    // the context's variance estimate is on exactly while the parameters ask for the variance-guided filter or renderUntil measures with it
+    // (a change restarts accumulation)
+    check(hiprz_set_variance(m_ctx, m_measuring || (params && (params->flags & HIPRZ_DENOISE_VARIANCE)) ? 1 : 0));
     check(hiprz_set_denoise(m_ctx, params));
     m_denoise = params != nullptr;
     if (params) m_denoise_params = *params;
+}
+
+void Engine::setMeasuring(bool enabled) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    m_measuring = enabled;
+    check(hiprz_set_variance(m_ctx, wantVariance()));
+}
+
+void Engine::noise(hiprz_noise_summary& out, float threshold, uint32_t min_batches) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (m_camera_records.empty()) throw Exception(HIPRZ_ERR_STATE, "noise: no frame has been rendered");
+    check(hiprz_select_camera(m_ctx, 0u));
+    const void *accum = nullptr, *variance = nullptr;
+    check(hiprz_variance_device(m_ctx, &variance));  // refuses first while the estimate is off
+    check(hiprz_accum_device(m_ctx, &accum));
+    if (!m_meter)
+        if (const int rc = hiprz_noise_create(&m_meter, m_device); rc != HIPRZ_OK) throw Exception(rc, hiprz_noise_last_error(nullptr));
+    const hiprz_camera& cam = m_camera_records[0];
+    const hiprz_noise_params params{cam.aperture, cam.exposure_time, threshold, min_batches};
+    const int rc = hiprz_noise_measure(m_meter, accum, variance, cam.width, cam.height, &params, hiprz_stream(m_ctx), &out, nullptr);
+    if (m_camera_records.size() > 1) check(hiprz_select_camera(m_ctx, uint32_t(m_camera_records.size() - 1)));  // where renderWorld left it
+    if (rc != HIPRZ_OK) throw Exception(rc, hiprz_noise_last_error(m_meter));
+}
+
+Engine::NoiseResult Engine::renderUntil(World& world, const RenderConfig& cfg, float target, uint32_t max_passes, uint32_t min_batches) {
+    if (max_passes < 1u || min_batches < 2u) throw Exception(HIPRZ_ERR_INVALID, "renderUntil: max_passes must be at least 1 and min_batches at least 2");
+    setMeasuring(true);
+    NoiseResult r{};
+    const uint32_t rpp = std::max(cfg.tracing.rpp, 1u);
+    bool measured = false;
+    for (uint32_t calls = 1; r.passes < max_passes && !r.met; ++calls) {
+        renderWorld(world, cfg, true, true);
+        r.passes += rpp, measured = false;
+        if (calls >= min_batches) {
+            noise(r.summary, 1.0f / 255.0f, min_batches);
+            measured = true;
+            r.met = r.summary.estimated == r.summary.pixels && r.summary.tile_rms_max <= double(target);
+        }
+    }
+    if (!measured) {  // fewer calls than min_batches: the frame as it stands (it may have been accumulating before this call)
+        noise(r.summary, 1.0f / 255.0f, min_batches);
+        r.met = r.summary.estimated == r.summary.pixels && r.summary.tile_rms_max <= double(target);
+    }
+    return r;
 }
 void Engine::tree(uint32_t tree) {
     std::lock_guard<std::mutex> lock(m_mutex);
@@ -418,7 +466,7 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));
                 check(hiprz_set_tree(m_ctx, m_tree));
-                check(hiprz_set_variance(m_ctx, m_denoise && (m_denoise_params.flags & HIPRZ_DENOISE_VARIANCE) ? 1 : 0));
+                check(hiprz_set_variance(m_ctx, wantVariance()));
                 check(hiprz_set_denoise(m_ctx, m_denoise ? &m_denoise_params : nullptr));
             }
         }

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "hiprz.h"
+#include "hiprz_noise.h"
 
 namespace RayZath::Hip {
 
@@ -235,6 +236,22 @@ public:
     // Parameters with HIPRZ_DENOISE_VARIANCE also switch the context's variance estimate on (hiprz_set_variance; every renderWorld call is
     // one batch), any others switch it off: a change of that restarts accumulation.
     void setDenoise(const hiprz_denoise_params* params);
+    // The noise level of the first camera's frame (include/hiprz_noise.h): the standard error of the displayed luminance per 32x8 tile,
+    // summarised; a pixel has an estimate once `min_batches` renderWorld calls closed a batch for it.  Needs the variance estimate
+    // (renderUntil or setDenoise with HIPRZ_DENOISE_VARIANCE switched it on): HIPRZ_ERR_STATE otherwise.  Waits for the stream; changes no frame.
+    void noise(hiprz_noise_summary& out, float threshold = 1.0f / 255.0f, uint32_t min_batches = 8);
+    // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
+    void setMeasuring(bool enabled);
+    // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
+    // estimate and summary.tile_rms_max <= target (display units), or until max_passes passes were rendered; measured after every call from
+    // the min_batches-th on.  tile_rms_max, not rms: noise concentrated in one region is not averaged away by a clean background.
+    // Switches the variance estimate on if it was off — a real change, which restarts accumulation — and leaves it on.
+    struct NoiseResult {
+        hiprz_noise_summary summary;  // the last measurement
+        uint32_t passes;              // rendered by this call
+        bool met;
+    };
+    NoiseResult renderUntil(World& world, const RenderConfig& render_config, float target, uint32_t max_passes, uint32_t min_batches = 8);
     ~Engine();
     Engine(const Engine&) = delete;
     Engine& operator=(const Engine&) = delete;
@@ -263,6 +280,9 @@ private:
     uint32_t m_mode = 0, m_tree = HIPRZ_TREE_AUTO;  // what mode() / tree() set (the hosts' default trees: per scene), for the context that replaces it
     bool m_denoise = false;
     hiprz_denoise_params m_denoise_params{};
+    bool m_measuring = false;               // renderUntil was called: the variance estimate stays on for its measurements
+    hiprz_noise_meter* m_meter = nullptr;   // on the head device, created at the first measurement
+    int wantVariance() const { return m_measuring || (m_denoise && (m_denoise_params.flags & HIPRZ_DENOISE_VARIANCE)) ? 1 : 0; }
     std::mutex m_mutex;  // renderWorld is serialised (cpu_engine_core.cpp:15)
     bool m_pending_readback = false;
     struct PendingFrame {  // a frame a non-sync call presented: the next call hands it out once its own renders are enqueued

@@ -472,6 +472,16 @@ int hiprz_read_accum(hiprz_ctx* c, float* dst, size_t bytes) {
     return read_image(c, reinterpret_cast<float4*>(dst), bytes, "read accum", [c] { return assemble_accum_image(c); });
 }
 
+int hiprz_accum_device(hiprz_ctx* c, const void** out) {
+    if (!c) return HIPRZ_ERR_INVALID;
+    if (!out) return fail(c, HIPRZ_ERR_INVALID, "accum_device: null output");
+    if (c->is_peer) return fail(c, HIPRZ_ERR_STATE, "accum_device on a part of a multi-device context");
+    if (!c->have_scene || !c->have_camera) return fail(c, HIPRZ_ERR_STATE, "accum_device before scene and camera upload");
+    if (const int rc = assemble_accum_image(c); rc != HIPRZ_OK) return rc;
+    *out = c->image_f4.ptr;
+    return HIPRZ_OK;
+}
+
 int hiprz_read_state(hiprz_ctx* c, float* ray9, uint32_t* md2, size_t n_pixels) {
     if (!c) return HIPRZ_ERR_INVALID;
     if (!c->have_camera) return fail(c, HIPRZ_ERR_STATE, "readback before camera upload");

@@ -89,6 +89,9 @@ class Context:
         self.width = self.height = 0
         self._sizes = {}
         self._presented = {}  # camera -> sequence of its newest present
+        self._head_device = int(device[0]) if isinstance(device, (list, tuple)) else int(device)
+        self._meter = None    # noise(): a hiprz_noise_meter on the head device, created at the first measurement
+        self._exposure = {}   # camera -> (aperture, exposure_time) as uploaded: the k of the tone curve noise() measures through
 
     def device_count(self):
         v = C.c_uint32()
@@ -122,6 +125,9 @@ class Context:
                                                   f.direct_lights.ctypes.data, len(f.direct_lights)))
 
     def close(self):
+        if getattr(self, "_meter", None) is not None:
+            self._meter.close()
+            self._meter = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -146,12 +152,14 @@ class Context:
         if (self.width, self.height) != (camera_struct_.width, camera_struct_.height):
             self._presented[getattr(self, "_camera", 0)] = 0  # a resize restarts the camera's sequence
         self.width, self.height = camera_struct_.width, camera_struct_.height
+        self._exposure[getattr(self, "_camera", 0)] = (float(camera_struct_.aperture), float(camera_struct_.exposure_time))
 
     def set_config(self, config_struct):
         self._check(self.lib.hiprz_set_config(self._ctx, C.byref(config_struct)))
 
     def set_shard(self, rank, world):
         self._check(self.lib.hiprz_set_shard(self._ctx, rank, world))
+        self._shard_world = int(world)
 
     def set_shard_mode(self, mode):
         """How the parts of a context over several devices / streams divide its share (hiprz_set_shard_mode): SHARD_TILES (default) —
@@ -392,6 +400,28 @@ class Context:
         self._check(self.lib.hiprz_variance_device(self._ctx, C.byref(v)))
         return v.value
 
+    def accum_device(self):
+        """hiprz_accum_device: the accumulator image of read_accum() on the head device, enqueued on stream(); valid until the next call
+        that reads back, denoises or presents."""
+        v = C.c_void_p()
+        self._check(self.lib.hiprz_accum_device(self._ctx, C.byref(v)))
+        return v.value
+
+    # --- noise level: a per-tile error map in display units and its summary (include/hiprz_noise.h) ---
+    def noise(self, threshold=1.0 / 255.0, min_batches=8):
+        """The noise level of the selected camera's frame: (noise.Summary, tiles (tiles_y, tiles_x, 4) float32 of (sum e^2, max e,
+        n_estimated, n_above)), e the standard error of a pixel's displayed luminance.  Needs set_variance(1) (HIPRZ_ERR_STATE otherwise):
+        a pixel has an estimate once `min_batches` render calls closed a batch for it — 8 is where the estimate's own relative error,
+        sqrt(2 / (K - 1)), is about 0.5.  `threshold`: pixels with e above it are counted.  Waits for the stream; changes no frame."""
+        from . import noise as _noise
+        variance = self.variance_device()  # refuses first: off, or before scene and camera
+        accum = self.accum_device()
+        if self._meter is None:
+            self._meter = _noise.Meter(self._head_device)
+        aperture, exposure_time = self._exposure[getattr(self, "_camera", 0)]
+        params = _noise.Params(aperture, exposure_time, float(threshold), int(min_batches))
+        return self._meter.measure(accum, variance, self.width, self.height, params, self.stream())
+
     def selftest(self, cases_per_thread=64, seed=1):
         bad, n = C.c_uint64(), C.c_uint64()
         self._check(self.lib.hiprz_selftest(self._ctx, cases_per_thread, seed, C.byref(bad), C.byref(n)))
@@ -477,6 +507,7 @@ class Engine:
         (with variance=True the context's variance estimate is switched on: every renderWorld call is one batch)."""
         self._device, self._streams, self._context = device, streams, None
         self._denoise = denoise
+        self._measuring = False  # render_until() was called: the variance estimate stays on for its measurements
         self._pipelined = pipelined
         self._pending = []  # pipelined, sync=False: (camera slot, camera, sequence) presented by the previous call, not yet handed out
         self._tree = TREE_AUTO   # the hosts' default: the snapshot's trees for scenes staged in LDS, the device's surface-area trees otherwise
@@ -499,8 +530,9 @@ class Engine:
             self._apply_denoise()
 
     def _apply_denoise(self):
-        """the context's filter parameters, and its variance estimate on exactly while they ask for the variance-guided filter"""
-        self._context.set_variance(_wants_variance(self._denoise))
+        """the context's filter parameters, and its variance estimate on exactly while they ask for the variance-guided filter or
+        render_until() measures the noise level with it"""
+        self._context.set_variance(_wants_variance(self._denoise) or self._measuring)
         self._context.set_denoise(self._denoise)
 
     def set_tree(self, tree):
@@ -606,6 +638,52 @@ class Engine:
                     self._deliver(ctx, cam, world, ctx.read_frame(seq))
             if pending and cameras:
                 ctx.select_camera(len(cameras) - 1)
+
+    def render_until(self, world, render_config, target, max_passes, min_batches=8):
+        """Render to a noise target: renderWorld calls (each one batch of tracing.rpp passes) until EVERY pixel of the frame has an
+        estimate and the worst tile's rms error is at most `target` (display units: 1/255 is one step of RGBA8), or until `max_passes`
+        passes were rendered.  From the `min_batches`-th call on the frame is measured after every call (Context.noise).  The rule reads
+        tile_rms_max, not rms: noise concentrated in one region is not averaged away by a clean background.  Returns (noise.Summary of the
+        last measurement, passes rendered by this call, met).
+        The variance estimate is switched on if it was off — a real change, which restarts accumulation — and stays on afterwards.  The
+        world's first camera is the one measured.  Refused (HIPRZ_ERR_STATE) on a context that renders one shard of a frame
+        (Context.set_shard with world > 1): it does not hold the frame."""
+        rpp = max(int(render_config.tracing.rpp), 1)
+        if int(max_passes) < 1 or int(min_batches) < 2:
+            raise ValueError("render_until: max_passes must be at least 1 and min_batches at least 2")
+
+        def refuse_shards():
+            if getattr(self._context, "_shard_world", 1) > 1:
+                raise HiprzError(_abi.ERR_STATE, "render_until: this context renders one shard of the frame (set_shard) and does not hold it")
+
+        if self._context is not None:
+            refuse_shards()
+        if not self._measuring:
+            self._measuring = True
+            if self._context is not None:
+                self._apply_denoise()
+
+        def rule(s):
+            return s.estimated == s.pixels and s.tile_rms_max <= target
+
+        summary, passes, calls, met = None, 0, 0, False
+        while passes < max_passes and not met:
+            self.renderWorld(world, render_config)
+            refuse_shards()
+            calls, passes, summary = calls + 1, passes + rpp, None
+            if calls >= min_batches:
+                summary = self._measure(min_batches)
+                met = rule(summary)
+        if summary is None:  # fewer calls than min_batches: the frame as it stands (it may have been accumulating before this call)
+            summary = self._measure(min_batches)
+            met = rule(summary)
+        return summary, passes, met
+
+    def _measure(self, min_batches):
+        ctx = self._context
+        if ctx.camera_count() > 1:
+            ctx.select_camera(0)
+        return ctx.noise(min_batches=min_batches)[0]
 
     @staticmethod
     def _deliver(ctx, cam, world, frame):
