@@ -576,16 +576,26 @@ static void analyze_intersection(const kctx* k, const traversal_t* tr, surface_t
     const hiprz_material* m = &s->materials[sf->surface_material];
     /* The reference indexes mesh.texcrds() unconditionally inside mapNormal (UB for a
      * triangle without texcrds); such triangles are shaded here as if unmapped. */
+    int mapped = 0;
     if (m->normal_map >= 0 && has_texcrds) {
         const col map_color = (k->flags & HIPRZ_COMPAT_FILTERING) ? compat_map(k, m->normal_map, sf->u, sf->v)
                                                                    : fetch_rgba8(k, m->normal_map, sf->u, sf->v);
         map_normal(tri, at, map_color, &sf->mapped_normal, v3_from(in->scale));
+#ifdef RZ_MUT_GUIDE_MAP_SCALED /* mutant: the normal a map gave is transformed with the scale, like an unmapped one */
+        sf->mapped_normal = transform_l2g(in, sf->mapped_normal);
+#else
         sf->mapped_normal = transform_l2g_noscale(in, sf->mapped_normal);
+#endif
+        mapped = 1;
     } else {
         sf->mapped_normal = transform_l2g(in, sf->mapped_normal);
     }
     sf->mapped_normal = v3_normalized(sf->mapped_normal);
+#ifdef RZ_MUT_GUIDE_NO_FLIP /* mutant: the normal a map gave is not turned towards the ray on an internal hit */
+    if (!mapped)
+#endif
     sf->mapped_normal = v3_scale(sf->mapped_normal, external_factor);
+    (void)mapped;
 
     sf->normal = v3_scale(v3_from(at->face_normal), external_factor);
     sf->normal = transform_l2g(in, sf->normal);
@@ -1262,6 +1272,37 @@ typedef struct {
     v3 point, next_direction;
 } tracing_result;
 
+/* The colour and the emission of a surface as traceRay reads them (cpu_engine_kernel.cpp:128-129; cuda_render_kernel.cu:158-159): one
+ * copy for trace_ray and for the first-hit records of rzo_first_hit, which must see the colour the first pass sees.  The RZ_MUT_GUIDE_*
+ * mutants of this function are bugs of a guide kernel that does not follow the integrator's branch. */
+static void surface_color_emission(const kctx* k, const hiprz_material* sm, surface_t* sf) {
+    uint32_t flags = k->flags;
+    hiprz_material plain;
+    kctx other;
+#ifdef RZ_MUT_GUIDE_COLOR_ONLY /* mutant: the material's colour also where a texture is set */
+    plain = *sm, plain.texture = -1, sm = &plain;
+#endif
+#ifdef RZ_MUT_GUIDE_POINT_FETCH /* mutant: the texture object's filter and address modes ignored: the CPU engine's point / wrap read */
+    flags &= ~HIPRZ_COMPAT_FILTERING;
+#endif
+#ifdef RZ_MUT_GUIDE_REPLACE /* mutant: the texture replaces the colour (and the map the emission) under HIPRZ_COMPAT_TEXTURE_MULT too */
+    flags &= ~HIPRZ_COMPAT_TEXTURE_MULT;
+#endif
+    (void)plain;
+    other = *k, other.flags = flags, k = &other;
+    if (flags & HIPRZ_COMPAT_TEXTURE_MULT) { /* opacityColor(texcrd), emission(texcrd): cuda_render_kernel.cu:158-159 */
+        sf->color = compat_opacity_color(k, sm, sf->u, sf->v);
+        sf->emission = compat_emission(k, sm, sf->u, sf->v);
+    } else if (flags & HIPRZ_COMPAT_FILTERING) { /* the CPU engine's fetchColor / fetchEmission, read through the texture object */
+        sf->color = sm->texture >= 0 ? compat_map(k, sm->texture, sf->u, sf->v) : col_from_u8(sm->color);
+        sf->color.a = 1.0f - sf->color.a;
+        sf->emission = sm->emission_map >= 0 ? compat_map(k, sm->emission_map, sf->u, sf->v).r : sm->emission;
+    } else {
+        sf->color = fetch_color(k, sm, sf->u, sf->v);
+        sf->emission = fetch_emission(k, sm, sf->u, sf->v);
+    }
+}
+
 static tracing_result trace_ray(const kctx* k, tracing_state* ts, ray_t* ray, rng_t* rng) {
     tracing_result result;
     memset(&result, 0, sizeof result);
@@ -1294,17 +1335,7 @@ static tracing_result trace_ray(const kctx* k, tracing_state* ts, ray_t* ray, rn
     }
     const hiprz_material* sm = &k->s->materials[sf.surface_material];
 
-    if (k->flags & HIPRZ_COMPAT_TEXTURE_MULT) { /* opacityColor(texcrd), emission(texcrd): cuda_render_kernel.cu:158-159 */
-        sf.color = compat_opacity_color(k, sm, sf.u, sf.v);
-        sf.emission = compat_emission(k, sm, sf.u, sf.v);
-    } else if (k->flags & HIPRZ_COMPAT_FILTERING) { /* the CPU engine's fetchColor / fetchEmission, read through the texture object */
-        sf.color = sm->texture >= 0 ? compat_map(k, sm->texture, sf.u, sf.v) : col_from_u8(sm->color);
-        sf.color.a = 1.0f - sf.color.a;
-        sf.emission = sm->emission_map >= 0 ? compat_map(k, sm->emission_map, sf.u, sf.v).r : sm->emission;
-    } else {
-        sf.color = fetch_color(k, sm, sf.u, sf.v);
-        sf.emission = fetch_emission(k, sm, sf.u, sf.v);
-    }
+    surface_color_emission(k, sm, &sf);
     if (k->flags & HIPRZ_COMPAT_BEER_LAMBERT) { /* Beer's law, cuda_render_kernel.cu:161-176: before the emission term */
         const hiprz_material* medium = &k->s->materials[ray->material];
         col op = col_from_u8(medium->color); /* opacityColor(), cuda_material.cuh:80-85 */
@@ -1610,6 +1641,89 @@ void rzo_pick(const hiprz_scene* scene, const hiprz_camera* camera, const rzo_co
         *instance_out = tr.closest_instance;
         *material_out = slot < in->material_count ? scene->inst_materials[in->material_base + slot] : -1;
     }
+}
+
+/* The same ray cast with everything hiprz_raycast holds: the triangle's material slot as Instance::material is asked for it and the
+ * triangle's index in its mesh as well. */
+void rzo_ray_cast(const hiprz_scene* scene, const hiprz_camera* camera, const rzo_context* ctx, uint32_t x, uint32_t y,
+                  hiprz_raycast* out) {
+    hiprz_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    kctx k = {scene, camera, &cfg, NULL, 0u};
+    ray_t ray;
+    memset(&ray, 0, sizeof ray);
+    generate_simple_ray(camera, &ray, x, y);
+    const float depth = ctx->depth[(size_t)y * ctx->width + x];
+    ray.near_ = depth * 0.99f;
+    ray.far_ = depth * 1.01f;
+    traversal_t tr;
+    out->instance = out->material_slot = out->material = -1;
+    out->triangle = 0u;
+    closest_intersection(&k, &ray, NULL, &tr);
+    if (tr.closest_instance >= 0) {
+        const hiprz_instance* in = &scene->instances[tr.closest_instance];
+        const hiprz_tri* tri = &scene->tris[tr.closest_triangle];
+        uint32_t slot = tri->material_flags & HIPRZ_TRI_MATERIAL_MASK;
+        if (slot > 63u) slot = 63u;
+        out->instance = tr.closest_instance;
+        out->material_slot = (int32_t)slot;
+        out->material = slot < in->material_count ? scene->inst_materials[in->material_base + slot] : -1;
+        out->triangle = tri->source_index;
+    }
+}
+
+/* The geometric first hit of pixel (x, y) as the first pass's shading sees it, for the guide buffers of the denoiser (hiprz.h:
+ * hiprz_guide): renderFirstPass's pixel-centre ray (cpu_engine_kernel.cpp:15-24), closestIntersection with a zeroed surface, then the
+ * colour / emission branch of traceRay for `flags`.  No random number is drawn and the medium does not scatter the ray. */
+void rzo_first_hit(const hiprz_scene* scene, const hiprz_camera* camera, uint32_t flags, uint32_t x, uint32_t y,
+                   rzo_first_hit_record* out) {
+    hiprz_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    kctx k = {scene, camera, &cfg, NULL, flags & ~HIPRZ_COMPAT_REPROJECTION};
+    ray_t ray;
+    memset(&ray, 0, sizeof ray);
+    generate_simple_ray(camera, &ray, x, y);
+    surface_t sf;
+    memset(&sf, 0, sizeof sf);
+    traversal_t tr;
+    memset(out, 0, sizeof *out);
+    const int found = closest_intersection(&k, &ray, &sf, &tr);
+    out->depth = ray.far_;
+    out->albedo[0] = out->albedo[1] = out->albedo[2] = 1.0f;
+    out->instance = HIPRZ_GUIDE_MISS;
+    out->triangle = out->material_slot = out->material = -1;
+    if (!found) return;
+    const hiprz_tri* tri = &scene->tris[tr.closest_triangle];
+    surface_color_emission(&k, &scene->materials[sf.surface_material], &sf);
+    out->normal[0] = sf.mapped_normal.x, out->normal[1] = sf.mapped_normal.y, out->normal[2] = sf.mapped_normal.z;
+#ifdef RZ_MUT_GUIDE_EMISSIVE_ALBEDO /* mutant: the albedo kept where the hit emits */
+    if (1) {
+#else
+    if (!(sf.emission > 0.0f)) {
+#endif
+        out->albedo[0] = sf.color.r, out->albedo[1] = sf.color.g, out->albedo[2] = sf.color.b;
+    }
+    out->instance = (uint32_t)tr.closest_instance;
+    out->triangle = tr.closest_triangle;
+    out->source_index = tri->source_index;
+    uint32_t slot = tri->material_flags & HIPRZ_TRI_MATERIAL_MASK;
+    if (slot > 63u) slot = 63u;
+    out->material_slot = (int32_t)slot;
+    out->material = sf.surface_material == HIPRZ_MATERIAL_DEFAULT ? -1 : (int32_t)sf.surface_material;
+    out->external = (uint32_t)tr.external;
+    out->u = sf.u, out->v = sf.v;
+    out->emission = sf.emission;
+}
+void rzo_first_hit_frame(const hiprz_scene* scene, const hiprz_camera* camera, uint32_t flags, rzo_first_hit_record* out, int threads) {
+#ifdef _OPENMP
+    if (threads <= 0) threads = omp_get_num_procs();
+#else
+    threads = 1;
+#endif
+    const int n = (int)(camera->width * camera->height);
+#pragma omp parallel for num_threads(threads) schedule(static)
+    for (int p = 0; p < n; ++p)
+        rzo_first_hit(scene, camera, flags, (uint32_t)p % camera->width, (uint32_t)p / camera->width, &out[p]);
 }
 
 /* ------------------------------------------------------------------------------------

@@ -69,6 +69,31 @@ void rzo_render_pass_mode(const hiprz_scene* scene, const hiprz_camera* camera, 
 void rzo_pick(const hiprz_scene* scene, const hiprz_camera* camera, const rzo_context* ctx, uint32_t x,
               uint32_t y, int32_t* instance_out, int32_t* material_out);
 
+/* The same ray cast with all four fields of hiprz_raycast (instance, material slot, material, the triangle's index in its mesh). */
+void rzo_ray_cast(const hiprz_scene* scene, const hiprz_camera* camera, const rzo_context* ctx, uint32_t x, uint32_t y,
+                  hiprz_raycast* out);
+
+/* The geometric first hit of a pixel as the first pass's shading sees it: renderFirstPass's pixel-centre ray, closestIntersection with a
+ * zeroed surface, and the colour / emission branch traceRay takes for `flags` (HIPRZ_COMPAT_*; 0 = the CPU engine).  No random number,
+ * no scattering step.  The first 32 bytes are the pixel's hiprz_guide as hiprz.h specifies it; the rest classifies the hit. */
+typedef struct rzo_first_hit_record {
+    float normal[3];       /* Surface::mapped_normal facing the ray; 0 on a miss                              */
+    float depth;           /* ray.far_ after the walk                                                          */
+    float albedo[3];       /* the colour's rgb; 1 on a miss and where emission > 0                             */
+    uint32_t instance;     /* HIPRZ_GUIDE_MISS on a miss                                                       */
+    int32_t triangle;      /* global index into hiprz_scene::tris, -1 on a miss                                */
+    uint32_t source_index; /* the triangle's index in its mesh                                                 */
+    int32_t material_slot; /* the triangle's material id clamped to 63, -1 on a miss                           */
+    int32_t material;      /* index into hiprz_scene::materials, -1 = slot unset (the default material) / miss */
+    uint32_t external;     /* the ray met the triangle's front                                                 */
+    float u, v;            /* Surface::texcrd                                                                  */
+    float emission;        /* the emission the branch fetched                                                  */
+} rzo_first_hit_record;
+void rzo_first_hit(const hiprz_scene* scene, const hiprz_camera* camera, uint32_t flags, uint32_t x, uint32_t y,
+                   rzo_first_hit_record* out);
+/* ... of every pixel, row-major, on `threads` workers (<= 0: all hardware threads) */
+void rzo_first_hit_frame(const hiprz_scene* scene, const hiprz_camera* camera, uint32_t flags, rzo_first_hit_record* out, int threads);
+
 /* Independent restatement of the host tree builders (bvh_tree_node.hpp:117-215,
  * component_container.hpp:259-363) with the flattened output layout of hiprz.h — used to
  * check hiprz_build_mesh_tree / hiprz_build_world_tree node-for-node. */

@@ -22,6 +22,12 @@ class _Ctx(C.Structure):
                 ("rgba8", C.POINTER(C.c_uint8)), ("passes", C.c_uint32), ("traced_rays", C.c_uint64)]
 
 
+# rzo_first_hit_record: the pixel's hiprz_guide (_abi.guide_dtype, 32 bytes) and what classifies the hit
+first_hit_dtype = np.dtype([("normal", "<f4", 3), ("depth", "<f4"), ("albedo", "<f4", 3), ("instance", "<u4"), ("triangle", "<i4"),
+                            ("source_index", "<u4"), ("material_slot", "<i4"), ("material", "<i4"), ("external", "<u4"), ("u", "<f4"),
+                            ("v", "<f4"), ("emission", "<f4")])
+assert first_hit_dtype.itemsize == 64
+
 _lib = None
 _variants = {}
 
@@ -51,6 +57,10 @@ def load(path=LIB_PATH):
     lib.rzo_pick.restype = None
     lib.rzo_pick.argtypes = [C.POINTER(_abi.Scene), C.POINTER(_abi.Camera), C.POINTER(_Ctx), U32, U32,
                              C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.rzo_ray_cast.restype = None
+    lib.rzo_ray_cast.argtypes = [C.POINTER(_abi.Scene), C.POINTER(_abi.Camera), C.POINTER(_Ctx), U32, U32, C.POINTER(_abi.RayCast)]
+    lib.rzo_first_hit.restype, lib.rzo_first_hit.argtypes = None, [C.POINTER(_abi.Scene), C.POINTER(_abi.Camera), U32, U32, U32, P]
+    lib.rzo_first_hit_frame.restype, lib.rzo_first_hit_frame.argtypes = None, [C.POINTER(_abi.Scene), C.POINTER(_abi.Camera), U32, P, C.c_int]
     lib.rzo_seed_value.restype, lib.rzo_seed_value.argtypes = F, [U32, U32, U32]
     lib.rzo_rng_sequence.restype, lib.rzo_rng_sequence.argtypes = None, [F, F, F, U32, P]
     lib.rzo_box_test.restype, lib.rzo_box_test.argtypes = C.c_int, [P, P, P, P, F, F]
@@ -157,6 +167,37 @@ class OracleRenderer:
         i, m = C.c_int32(), C.c_int32()
         self.lib.rzo_pick(C.byref(self.scene.struct), C.byref(self.camera), self.ctx, x, y, C.byref(i), C.byref(m))
         return i.value, m.value
+
+    def ray_cast(self, x, y):
+        """(instance, material slot, material, the triangle's index in its mesh) as Context.ray_cast returns them"""
+        r = _abi.RayCast()
+        self.lib.rzo_ray_cast(C.byref(self.scene.struct), C.byref(self.camera), self.ctx, x, y, C.byref(r))
+        return r.instance, r.material_slot, r.material, r.triangle
+
+
+def first_hits(flat_scene, camera, mode=0, lib=None, threads=1):
+    """(H, W) array of first_hit_dtype: rzo_first_hit of every pixel under the HIPRZ_COMPAT_* flags `mode`.  The view
+    guides(records) is what Context.read_guides must return."""
+    lib = lib or load()
+    out = np.zeros((camera.height, camera.width), first_hit_dtype)
+    lib.rzo_first_hit_frame(C.byref(flat_scene.struct), C.byref(camera), int(mode), out.ctypes.data, threads)
+    return out
+
+
+def first_hit(flat_scene, camera, x, y, mode=0, lib=None):
+    """one pixel's record, by the per-pixel entry point"""
+    lib = lib or load()
+    out = np.zeros(1, first_hit_dtype)
+    lib.rzo_first_hit(C.byref(flat_scene.struct), C.byref(camera), int(mode), x, y, out.ctypes.data)
+    return out[0]
+
+
+def guides(records):
+    """the hiprz_guide part of first-hit records as an array of _abi.guide_dtype"""
+    out = np.zeros(records.shape, _abi.guide_dtype)
+    for name in _abi.guide_dtype.names:
+        out[name] = records[name]
+    return out
 
 
 def compat_fetch(flat_scene, texture, u, v, lib=None):
