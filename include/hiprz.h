@@ -502,6 +502,13 @@ int hiprz_tonemap_image(hiprz_ctx* ctx, const void* src_device_image, void* dst_
 /* The same on `stream` (a hipStream_t; NULL = the context's stream): the stream a reduce of the accumulators ran on. */
 int hiprz_tonemap_image_on(hiprz_ctx* ctx, const void* src_device_image, void* dst_device_rgba8, void* stream);
 void* hiprz_stream(hiprz_ctx* ctx); /* the hipStream_t all of the above are enqueued on */
+/* Host only, no kernel: copies of the device views the kernels are launched with — the head's scene view (DScene) and the selected camera's
+ * (DCamera), PODs of device pointers and sizes (rayzath_amd/csrc/hiprz_device.hpp) — for a library compiled from the same headers that
+ * launches kernels of its own on hiprz_stream (include/hiprz_query.h).  The views are valid until the next call that uploads, updates or
+ * rebuilds: fetch them per call.  HIPRZ_ERR_INVALID unless dscene_bytes and dcamera_bytes are the sizes of the structures as THIS library
+ * was compiled (dcamera NULL with dcamera_bytes 0: the scene alone); HIPRZ_ERR_STATE before a scene, for the camera half before a camera, and
+ * on a part of a multi-device context (a guard: no call hands a part's handle out today).  Makes the context's device the calling thread's current HIP device, as the other calls do. */
+int hiprz_device_view(hiprz_ctx* ctx, void* dscene, size_t dscene_bytes, void* dcamera, size_t dcamera_bytes);
 
 /* --- picking (Kernel::rayCast, cpu_engine_kernel.cpp:102-111, 483-501; Cuda: cuda_render_kernel.cu:130-144) ---
  * The reference casts one ray per camera and frame through the camera's ray-cast pixel (Camera::getRayCastPixel), in a thin shell

@@ -181,6 +181,7 @@ ENTRY_POINTS = {
     "hiprz_tonemap_image": (C.c_int, [P, P, P]),
     "hiprz_tonemap_image_on": (C.c_int, [P, P, P, P]),
     "hiprz_stream": (P, [P]),
+    "hiprz_device_view": (C.c_int, [P, P, SZ, P, SZ]),
     "hiprz_pick": (C.c_int, [P, U32, U32, C.POINTER(I32), C.POINTER(I32)]),
     "hiprz_ray_cast": (C.c_int, [P, U32, U32, C.POINTER(RayCast)]),
     "hiprz_present": (C.c_int, [P, U32, U32]),

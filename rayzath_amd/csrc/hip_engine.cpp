@@ -346,6 +346,7 @@ Engine::Engine(const std::vector<int>& devices) : m_device(devices.empty() ? 0 :
 }
 Engine::~Engine() {
     if (m_meter) hiprz_noise_destroy(m_meter);
+    if (m_query) hiprz_query_destroy(m_query);
     hiprz_destroy(m_ctx);
 }
 
@@ -392,6 +393,32 @@ void Engine::noise(hiprz_noise_summary& out, float threshold, uint32_t min_batch
     const int rc = hiprz_noise_measure(m_meter, accum, variance, cam.width, cam.height, &params, hiprz_stream(m_ctx), &out, nullptr);
     if (m_camera_records.size() > 1) check(hiprz_select_camera(m_ctx, uint32_t(m_camera_records.size() - 1)));  // where renderWorld left it
     if (rc != HIPRZ_OK) throw Exception(rc, hiprz_noise_last_error(m_meter));
+}
+
+hiprz_query* Engine::query() {
+    if (!m_query)
+        if (const int rc = hiprz_query_create(&m_query, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_query_last_error(nullptr));
+    return m_query;
+}
+
+std::vector<hiprz_hit> Engine::castRays(const std::vector<hiprz_ray>& rays, bool normalize) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    std::vector<hiprz_hit> hits(rays.size());
+    if (rays.empty()) return hits;
+    hiprz_query* q = query();
+    const int rc = hiprz_query_closest_host(q, rays.data(), rays.size(), normalize ? HIPRZ_QUERY_NORMALIZE : 0u, hits.data());
+    if (rc != HIPRZ_OK) throw Exception(rc, hiprz_query_last_error(q));
+    return hits;
+}
+
+std::vector<uint32_t> Engine::occluded(const std::vector<hiprz_ray>& rays, bool normalize) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    std::vector<uint32_t> out(rays.size());
+    if (rays.empty()) return out;
+    hiprz_query* q = query();
+    const int rc = hiprz_query_occluded_host(q, rays.data(), rays.size(), normalize ? HIPRZ_QUERY_NORMALIZE : 0u, out.data());
+    if (rc != HIPRZ_OK) throw Exception(rc, hiprz_query_last_error(q));
+    return out;
 }
 
 Engine::NoiseResult Engine::renderUntil(World& world, const RenderConfig& cfg, float target, uint32_t max_passes, uint32_t min_batches) {
@@ -462,6 +489,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
             hiprz_ctx* several = nullptr;
             const std::vector<int> ids(size_t(streams), m_device);
             if (hiprz_create_multi(&several, ids.data(), streams) == HIPRZ_OK) {
+                if (m_query) hiprz_query_destroy(m_query);  // bound to the context that goes
+                m_query = nullptr;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

@@ -24,6 +24,7 @@
 
 #include "hiprz.h"
 #include "hiprz_noise.h"
+#include "hiprz_query.h"
 
 namespace RayZath::Hip {
 
@@ -240,6 +241,10 @@ public:
     // summarised; a pixel has an estimate once `min_batches` renderWorld calls closed a batch for it.  Needs the variance estimate
     // (renderUntil or setDenoise with HIPRZ_DENOISE_VARIANCE switched it on): HIPRZ_ERR_STATE otherwise.  Waits for the stream; changes no frame.
     void noise(hiprz_noise_summary& out, float threshold = 1.0f / 255.0f, uint32_t min_batches = 8);
+    // Ray queries (include/hiprz_query.h): the closest hit / the occlusion of every ray of `rays` in the world of the last renderWorld call,
+    // in caller order; normalize: the device's normalized() is applied to the directions first.  Wait for the stream; change no frame.
+    std::vector<hiprz_hit> castRays(const std::vector<hiprz_ray>& rays, bool normalize = false);
+    std::vector<uint32_t> occluded(const std::vector<hiprz_ray>& rays, bool normalize = false);
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -282,6 +287,8 @@ private:
     hiprz_denoise_params m_denoise_params{};
     bool m_measuring = false;               // renderUntil was called: the variance estimate stays on for its measurements
     hiprz_noise_meter* m_meter = nullptr;   // on the head device, created at the first measurement
+    hiprz_query* m_query = nullptr;         // bound to m_ctx, created at the first query
+    hiprz_query* query();
     int wantVariance() const { return m_measuring || (m_denoise && (m_denoise_params.flags & HIPRZ_DENOISE_VARIANCE)) ? 1 : 0; }
     std::mutex m_mutex;  // renderWorld is serialised (cpu_engine_core.cpp:15)
     bool m_pending_readback = false;

@@ -1202,6 +1202,19 @@ int hiprz_pass_count(hiprz_ctx* c, uint32_t* out) {
 
 void* hiprz_stream(hiprz_ctx* c) { return c ? reinterpret_cast<void*>(c->stream) : nullptr; }
 
+int hiprz_device_view(hiprz_ctx* c, void* dscene, size_t dscene_bytes, void* dcamera, size_t dcamera_bytes) {
+    if (!c) return HIPRZ_ERR_INVALID;
+    if (!dscene || dscene_bytes != sizeof(DScene) || dcamera_bytes != (dcamera ? sizeof(DCamera) : 0u))
+        return fail(c, HIPRZ_ERR_INVALID, "device_view: the caller's device views are not this library's (built from other headers?)");
+    if (c->is_peer) return fail(c, HIPRZ_ERR_STATE, "device_view on a part of a multi-device context");
+    if (!c->have_scene) return fail(c, HIPRZ_ERR_STATE, "device_view before a scene upload");
+    if (dcamera && !c->have_camera) return fail(c, HIPRZ_ERR_STATE, "device_view: no camera has been uploaded");
+    (void)hipSetDevice(c->device);
+    std::memcpy(dscene, &c->dscene, sizeof(DScene));
+    if (dcamera) std::memcpy(dcamera, &c->dcamera, sizeof(DCamera));
+    return HIPRZ_OK;
+}
+
 uint32_t hiprz_kernel_count(void) { return uint32_t(kernel_table().size()); }
 
 int hiprz_selftest(hiprz_ctx* c, uint32_t cases_per_thread, uint32_t seed, uint64_t* mismatches, uint64_t* tested) {

@@ -128,6 +128,9 @@ class Context:
         if getattr(self, "_meter", None) is not None:
             self._meter.close()
             self._meter = None
+        if getattr(self, "_query", None) is not None:
+            self._query.close()
+            self._query = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -421,6 +424,38 @@ class Context:
         aperture, exposure_time = self._exposure[getattr(self, "_camera", 0)]
         params = _noise.Params(aperture, exposure_time, float(threshold), int(min_batches))
         return self._meter.measure(accum, variance, self.width, self.height, params, self.stream())
+
+    # --- ray queries: closest hit and occlusion for caller-supplied rays (include/hiprz_query.h) ---
+    def query(self):
+        """the context's query.Query, created at the first use (device-pointer calls: closest_device, occluded_device, pixel_rays_device)"""
+        from . import query as _query
+        if getattr(self, "_query", None) is None:
+            self._query = _query.Query(self._ctx)
+        return self._query
+
+    def trace(self, rays, normalize=False):
+        """The closest hit of every ray of `rays` (an array of query.ray_dtype) in the uploaded world: an array of query.hit_dtype of the
+        same shape.  normalize: the device's normalized() is applied to the directions first, t is then along the normalised direction;
+        otherwise the directions must be of unit length.  An invalid ray reads HIT_INVALID.  Waits for the stream; changes no frame."""
+        return self.query().closest(rays, normalize)
+
+    def occluded(self, rays, normalize=False):
+        """uint32 per ray: 1 = some triangle lies within (near, far) of the ray.  Waits for the stream; changes no frame."""
+        return self.query().occluded(rays, normalize)
+
+    def pixel_rays(self):
+        """(H, W) array of query.ray_dtype: the selected camera's pixel-centre rays, the ones the first pass, the guides and ray_cast walk"""
+        from . import _hiprt
+        from . import query as _query
+        q = self.query()
+        self.sync()  # (makes the head device the current one: the buffer below is allocated there)
+        buf = _hiprt.DeviceBuffer(self.width * self.height * _query.ray_dtype.itemsize)
+        try:
+            q.pixel_rays_device(buf.ptr)
+            self.sync()
+            return buf.download((self.height, self.width), _query.ray_dtype)
+        finally:
+            buf.free()
 
     def selftest(self, cases_per_thread=64, seed=1):
         bad, n = C.c_uint64(), C.c_uint64()
