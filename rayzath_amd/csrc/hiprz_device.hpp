@@ -148,6 +148,15 @@ RZ_DEV void repoint_hot(DScene& v, const unsigned char* base) {
 static_assert(sizeof(DScene) == 256, "off_pairs fills a padding word: the kernels' argument layout is what it was");
 RZ_DEV const unsigned char* pair_section(const DScene& s) { return reinterpret_cast<const unsigned char*>(s.nodes) - s.off_nodes + s.off_pairs; }
 
+// The surface records of a scene that may be staged in LDS (hiprz_scene_host.hpp: pack_surface_section): 16-byte aligned behind the
+// hot_bytes of the hot buffer, never staged — `hot` stays where it is when repoint_hot moves the sections, so this is global memory
+// (a few KB that live in the caches).  There is no word in DScene that says whether the section exists (sizeof(DScene) is pinned): every
+// upload whose scene use_lds_scene may stage builds it, and only the kernels that stage the scene read it.
+#ifndef RZ_SURFACE_RECORDS   // 0: the LDS_SCENE kernels derive normals and material ids per hit like every other kernel
+#define RZ_SURFACE_RECORDS 1
+#endif
+RZ_DEV const float4* surface_section(const DScene& s) { return s.hot + ((s.hot_bytes + 15u) >> 4); }
+
 struct DCamera {
     float position[3];
     float x_axis[3], y_axis[3], z_axis[3];
@@ -2418,9 +2427,54 @@ struct Surface {
     float surface_scattering;  // surface_material->scattering(), read with the material
 };
 
+// analyze_intersection from the hit's surface record (surface_section above): the material ids, the normal and — for a triangle without
+// vertex normals under a material without a normal map — the mapped normal are two 16-byte reads instead of four instance reads, the
+// attribute record, the slot lookup, six divisions, two transforms and two normalisations.  Returns false when the record cannot serve
+// (its normal is not valid: a subnormal or non-finite intermediate on the host; or the material has a normal map, whose tangent frame
+// needs everything anyway): the lane then runs the code below as if there were no record.
+template <bool TEX>
+RZ_DEV bool surface_from_record(const DScene& s, const Hit& hit, Surface& sf, Material& m) {
+    const float4* section = surface_section(s);
+    const uint32_t pair = reinterpret_cast<const uint32_t*>(section)[uint32_t(hit.instance)] + hit.triangle;
+    const float4* rec = section + ((s.n_instances + 3u) >> 2) + (size_t(pair) * 4u + (hit.external ? 2u : 0u));
+    const float4 ra = rec[0], rb = rec[1];
+    const uint32_t valid = __float_as_uint(rb.w);
+    if (!(valid & RZ_SURFACE_NORMAL_VALID)) return false;
+    sf.surface_material = __float_as_uint(ra.w);
+    sf.behind_material = hit.external ? sf.surface_material : HIPRZ_MATERIAL_WORLD;
+    m = load_material(s, sf.surface_material);
+    if (TEX && m.normal_map >= 0) return false;
+    sf.normal = xyz(ra);
+    if (TEX || !(valid & RZ_SURFACE_MAPPED_VALID)) {  // texture coordinates and vertex normals are per hit, as below
+        const uint32_t flags = __float_as_uint(s.tris[3 * hit.triangle].w);
+        const float4* at = s.tri_attrs + 6 * size_t(hit.triangle);
+        if (TEX && (flags & HIPRZ_TRI_HAS_TEXCRDS)) {
+            const float4 uv12 = at[4], uv3 = at[5];
+            const float b3 = 1.0f - hit.bx - hit.by;
+            sf.u = uv12.x * b3 + uv12.z * hit.bx + uv3.x * hit.by;
+            sf.v = uv12.y * b3 + uv12.w * hit.bx + uv3.y * hit.by;
+        }
+        if (!(valid & RZ_SURFACE_MAPPED_VALID)) {
+            const uint32_t inst = uint32_t(hit.instance);
+            const v3 scale = xyz(s.instances[7 * inst + 1]), xa = xyz(s.instances[7 * inst + 2]), ya = xyz(s.instances[7 * inst + 3]),
+                     za = xyz(s.instances[7 * inst + 4]);
+            v3 mn = xyz(at[3]);
+            if (flags & HIPRZ_TRI_HAS_NORMALS) mn = normalized(xyz(at[0]) * (1.0f - hit.bx - hit.by) + xyz(at[1]) * hit.bx + xyz(at[2]) * hit.by);
+            sf.mapped_normal = normalized(transform_forward(xa, ya, za, mn / scale)) * (float(hit.external) * 2.0f - 1.0f);
+            return true;
+        }
+    }
+    sf.mapped_normal = xyz(rb);
+    return true;
+}
+
 // analyzeIntersection: cpu_engine_kernel.cpp:354-395; mesh_component.cpp:115-167
-template <bool COUNT, bool TEX = true>
+// RECORDS: the scene has a surface section (the kernels that stage the scene in LDS, under RZ_SURFACE_RECORDS)
+template <bool COUNT, bool TEX = true, bool RECORDS = false>
 RZ_DEV void analyze_intersection(const DScene& s, const Hit& hit, Surface& sf, Material& m, Counters& cnt, bool compat_filtering = false) {
+    if constexpr (RECORDS) {
+        if (surface_from_record<TEX>(s, hit, sf, m)) return;
+    }
     const uint32_t inst = uint32_t(hit.instance);
     const float4 i1 = s.instances[7 * inst + 1], i2 = s.instances[7 * inst + 2],
                  i3 = s.instances[7 * inst + 3], i4 = s.instances[7 * inst + 4];

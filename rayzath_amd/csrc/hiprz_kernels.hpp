@@ -140,7 +140,9 @@ RZ_DEV void fetch_color_emission(const DScene& s, const Material& m, uint32_t fl
 // everything of traceRay after the closest hit (active lanes only): returns the segment's radiance and whether the path
 // goes on, and leaves the NEXT segment's ray / colour / material / depth in `ps` (TracingResult::repositionRay, or a fresh
 // antialiased camera ray when the path ended).  ps.ray.far_ must hold the hit distance.
-template <bool COUNT, int SHADOW = 1>
+// RECORDS: the scene has a surface section (hiprz_device.hpp: surface_from_record) — the kernels that stage the scene in LDS say so
+constexpr bool surface_records(bool lds_scene) { return lds_scene && RZ_SURFACE_RECORDS != 0; }
+template <bool COUNT, int SHADOW = 1, bool RECORDS = false>
 RZ_DEV void shade_segment(const DScene& s, const DCamera& cam, const DConfig& cfg, const PixelId& p, PathState& ps, uint32_t pass,
                           int found, const Hit& hit, const ShadowCtx& lds_column, Counters& cnt, col4& final_color, bool& path_continues,
                           Rng* shared_rng = nullptr) {
@@ -165,7 +167,7 @@ RZ_DEV void shade_segment(const DScene& s, const DCamera& cam, const DConfig& cf
     constexpr bool TEX = SHADOW != RZ_SHADOW_PLAIN;  // PLAIN: the scene has no maps at all (every map index is -1)
     Material m;
     if (found == 2) {
-        analyze_intersection<COUNT, TEX>(s, hit, sf, m, cnt, filtering);
+        analyze_intersection<COUNT, TEX, RECORDS>(s, hit, sf, m, cnt, filtering);
     } else if (COMPAT && found == 3) {  // Material::applyScattering: the medium itself is the surface, its normal the ray's direction
         m = load_material(s, ray_material);
         sf.surface_material = sf.behind_material = ray_material;
@@ -234,13 +236,13 @@ RZ_DEV void shade_segment(const DScene& s, const DCamera& cam, const DConfig& cf
 }
 
 // shade_segment + accumulation + next-segment state to HBM (renderFirstPass / renderCumulativePass after traceRay)
-template <bool FIRST, bool COUNT, int SHADOW = 1>
+template <bool FIRST, bool COUNT, int SHADOW = 1, bool RECORDS = false>
 RZ_DEV void shade_and_store(const DScene& s, const DCamera& cam, const DConfig& cfg, const DFrame& f, const PixelId& p, PathState& ps,
                             int found, const Hit& hit, const ShadowCtx& lds_column, Counters& cnt, Rng* shared_rng = nullptr) {
     const float hit_distance = ps.ray.far_;
     col4 final_color;
     bool path_continues;
-    shade_segment<COUNT, SHADOW>(s, cam, cfg, p, ps, FIRST ? 0u : *f.pass, found, hit, lds_column, cnt, final_color, path_continues, shared_rng);
+    shade_segment<COUNT, SHADOW, RECORDS>(s, cam, cfg, p, ps, FIRST ? 0u : *f.pass, found, hit, lds_column, cnt, final_color, path_continues, shared_rng);
     const Ray& ray = ps.ray;
     const col4& ray_color = ps.color;
     const uint32_t ray_material = ps.material, depth = ps.depth;
@@ -347,7 +349,7 @@ __global__ void __launch_bounds__(256, RZ_MIN_WAVES) rz_pass_kernel(const DScene
     } else {
         found = trace_path<MODE, COUNT, RZ_FUSED_SHARED_RCP != 0>(s, world, workspace, lds_column, p.active, ps.ray, hit, cnt);
     }
-    if (p.active) shade_and_store<FIRST, COUNT>(s, cam, cfg, f, p, ps, found, hit, ShadowCtx{lds_column, TopCache{nullptr, nullptr, 0u}}, cnt);
+    if (p.active) shade_and_store<FIRST, COUNT, 1, surface_records(LDS_SCENE)>(s, cam, cfg, f, p, ps, found, hit, ShadowCtx{lds_column, TopCache{nullptr, nullptr, 0u}}, cnt);
     flush_counters<COUNT>(f, p.active ? 1u : 0u, cnt);
 }
 
@@ -363,7 +365,7 @@ __global__ void __launch_bounds__(256, RZ_MIN_WAVES) rz_pass_kernel(const DScene
 // load_path does, and written there again at the end; the tone-mapped pixel only when `tonemap_out` (the batch's last pass).
 // `workspace` holds the walk's LDS, `park` (+ threadIdx.x) the thread's 8 parked words.  SC1: state and accumulator are handed to or
 // from another workgroup of the launch (load_state / store_state).
-template <bool COUNT, int MODE, int SHADING, bool SC1 = false>
+template <bool COUNT, int MODE, int SHADING, bool SC1 = false, bool RECORDS = false>
 RZ_DEV void batch_tile(const DScene& s, const DCamera& cam, const DConfig& cfg, const DFrame& f, unsigned char* workspace, uint32_t* park,
                        const PixelId& p, uint32_t pass0, uint32_t n_passes, bool tonemap_out, Counters& cnt) {
     uint32_t* lds_column = stack_column<MODE>(workspace);
@@ -398,7 +400,7 @@ RZ_DEV void batch_tile(const DScene& s, const DCamera& cam, const DConfig& cfg, 
         if (p.active) {
             col4 final_color;
             bool path_continues;
-            shade_segment<COUNT, SHADING>(s, cam, cfg, p, ps, pass0 + i, found, hit, ShadowCtx{lds_column, TopCache{nullptr, nullptr, 0u}}, cnt, final_color, path_continues);
+            shade_segment<COUNT, SHADING, RECORDS>(s, cam, cfg, p, ps, pass0 + i, found, hit, ShadowCtx{lds_column, TopCache{nullptr, nullptr, 0u}}, cnt, final_color, path_continues);
             park[4 * 256] = __float_as_uint(__uint_as_float(park[4 * 256]) + final_color.r);
             park[5 * 256] = __float_as_uint(__uint_as_float(park[5 * 256]) + final_color.g);
             park[6 * 256] = __float_as_uint(__uint_as_float(park[6 * 256]) + final_color.b);
@@ -432,7 +434,7 @@ __global__ void __launch_bounds__(256, WAVES) rz_batch_kernel(const DScene scene
     unsigned char* workspace = rz_lds + stage_scene<LDS_SCENE>(s, rz_lds);
     Counters cnt;
     uint32_t* park = reinterpret_cast<uint32_t*>(workspace + park_offset) + threadIdx.x;
-    batch_tile<COUNT, MODE, SHADING>(s, cam, cfg, f, workspace, park, p, *f.pass, n_passes, true, cnt);
+    batch_tile<COUNT, MODE, SHADING, false, surface_records(LDS_SCENE)>(s, cam, cfg, f, workspace, park, p, *f.pass, n_passes, true, cnt);
     if (f.unit_cost && threadIdx.x == 0u) {  // what this unit's batch cost: the next launches start the expensive units first
         const unsigned long long dt = (__builtin_readcyclecounter() - t_start) >> 4;
         f.unit_cost[unit] = dt < 0x00FFFFFFull ? uint32_t(dt) : 0x00FFFFFFu;
@@ -487,7 +489,7 @@ __global__ void __launch_bounds__(256, WAVES) rz_batch_seg_kernel(const DScene s
             const unsigned long long t_start = __builtin_readcyclecounter();
             const uint32_t first = k * n_passes / segments, end = (k + 1u) * n_passes / segments;
             Counters cnt;
-            batch_tile<COUNT, MODE, SHADING, true>(s, cam, cfg, f, workspace, park, p, pass_base + first, end - first, k + 1u == segments, cnt);
+            batch_tile<COUNT, MODE, SHADING, true, surface_records(LDS_SCENE)>(s, cam, cfg, f, workspace, park, p, pass_base + first, end - first, k + 1u == segments, cnt);
             if (f.unit_cost && threadIdx.x == 0u) {  // the tile's cost is the sum over its segments (launch_order keeps its meaning)
                 const uint32_t before = k != 0u ? __hip_atomic_load(&f.unit_cost[unit], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
                 const unsigned long long dt = ((__builtin_readcyclecounter() - t_start) >> 4) + before;
@@ -724,9 +726,9 @@ __global__ void __launch_bounds__(256, RZ_MIN_WAVES) rz_shade_kernel(const DScen
             const uint32_t pass = FIRST ? 0u : *f.pass, pixel_idx = p.y * cam.width + p.x;
             Rng rng(float(p.x) / float(cam.width), float(p.y) / float(cam.height), seed_value(cfg.seed, pass, (pixel_idx + ps.depth) & 255u));
             if ((cfg.flags & HIPRZ_COMPAT_SCATTERING) && material_scattering(s, ps.material) > 1.0e-4f) (void)rng.unsignedUniform();
-            shade_and_store<FIRST, COUNT, SHADOW>(s, cam, cfg, f, p, ps, found, hit, shadow, cnt, &rng);
+            shade_and_store<FIRST, COUNT, SHADOW, surface_records(LDS_SCENE)>(s, cam, cfg, f, p, ps, found, hit, shadow, cnt, &rng);
         } else {
-            shade_and_store<FIRST, COUNT, SHADOW>(s, cam, cfg, f, p, ps, found, hit, shadow, cnt);
+            shade_and_store<FIRST, COUNT, SHADOW, surface_records(LDS_SCENE)>(s, cam, cfg, f, p, ps, found, hit, shadow, cnt);
         }
     } else if (f.sort_key && p.local < f.n_local_tiles * 256u) {
         f.sort_key[p.local] = 0x00FFFFFFu;  // slots outside the frame sort to the end

@@ -119,13 +119,17 @@ int build_shadow_world_tree(hiprz_ctx* c, const std::vector<hiprz_instance>& din
 // ---- hiprz_upload_scene, stage by stage ----
 
 // every copy of the upload, on the context's stream; synchronous on return (host staging and the caller's arrays may go away)
-int copy_scene(hiprz_ctx* c, const hiprz_scene& sc, const PackedScene& packed, bool device_trees) {
+int copy_scene(hiprz_ctx* c, const hiprz_scene& sc, const PackedScene& packed, const std::vector<uint8_t>& surface_section, bool device_trees) {
     (void)hipSetDevice(c->device);
-    if (packed.pair_section.empty()) {
+    if (packed.pair_section.empty() && surface_section.empty()) {
         RZ_HIP(c, c->hot.assign(packed.blob.data(), packed.blob.size(), c->stream));
-    } else {  // the pair records stand directly behind the blob: one hot buffer, staged as a whole (DScene::hot_bytes is the total)
+    } else {
+        // the pair records stand directly behind the blob: one hot buffer, staged as a whole (DScene::hot_bytes is the total); the surface
+        // records follow 16-byte aligned behind hot_bytes, in the buffer but outside what is counted and staged (hiprz_device.hpp: surface_section)
         std::vector<uint8_t> hot(packed.blob);
         hot.insert(hot.end(), packed.pair_section.begin(), packed.pair_section.end());
+        hot.resize((hot.size() + 15u) & ~size_t(15), 0);
+        hot.insert(hot.end(), surface_section.begin(), surface_section.end());
         RZ_HIP(c, c->hot.assign(hot.data(), hot.size(), c->stream));
         RZ_HIP(c, hipStreamSynchronize(c->stream));  // (`hot` goes away)
     }
@@ -273,7 +277,9 @@ int hiprz_upload_scene(hiprz_ctx* c, const hiprz_scene* sc) {
     c->have_scene = false;
     PackedScene packed;
     if (pack_scene(trees, std::move(derived), packed, error) != HIPRZ_OK) return scene_lost(c, fail(c, HIPRZ_ERR_INVALID, error));
-    int rc = copy_scene(c, trees.scene, packed, trees.device_trees());
+    // what analyze_intersection would derive per hit, for the kernels that stage the scene in LDS (any scene use_lds_scene may ever stage)
+    const std::vector<uint8_t> surface_section = pack_surface_section(trees, packed, chk.world_depth + chk.mesh_depth + 2u, kLdsPerCu);
+    int rc = copy_scene(c, trees.scene, packed, surface_section, trees.device_trees());
     if (rc != HIPRZ_OK) return scene_lost(c, rc);
     bind_scene(c, trees, packed, chk);
     if (trees.device_trees()) rc = build_device_trees(c, packed);

@@ -3,6 +3,7 @@
 #include "hiprz_scene_host.hpp"
 
 #include <algorithm>
+#include <cmath>
 
 namespace hiprz {
 
@@ -427,6 +428,115 @@ int pack_scene(const ChosenTrees& trees, DerivedTables&& derived, PackedScene& o
     for (uint32_t i = 0; i < sc->n_instances; ++i)
         if (member[i]) out.world_members.push_back(i);
     return HIPRZ_OK;
+}
+
+namespace {
+
+// fp32 arithmetic of one surface record, every operation rounded on its own as the device rounds it (hiprz_device.hpp: v3 operators,
+// transform_forward, normalized); `bad` collects whether any value that went in or came out was subnormal, infinite or NaN
+struct SurfaceMath {
+    bool bad = false;
+    float see(float x) {
+        uint32_t b;
+        std::memcpy(&b, &x, 4);
+        const uint32_t e = (b >> 23) & 0xFFu;
+        if (e == 0xFFu || (e == 0u && (b & 0x007FFFFFu) != 0u)) bad = true;
+        return x;
+    }
+    void scaled(const float v[3], float s, float out[3]) {
+        for (int a = 0; a < 3; ++a) out[a] = see(v[a] * s);
+    }
+    void divided(const float v[3], const float d[3], float out[3]) {
+        for (int a = 0; a < 3; ++a) out[a] = see(v[a] / d[a]);
+    }
+    void forward(const hiprz_instance& in, const float v[3], float out[3]) {  // (xa * v.x + ya * v.y) + za * v.z
+        for (int a = 0; a < 3; ++a) {
+            const float x = see(in.x_axis[a] * v[0]), y = see(in.y_axis[a] * v[1]), z = see(in.z_axis[a] * v[2]);
+            out[a] = see(see(x + y) + z);
+        }
+    }
+    void normalize(const float v[3], float out[3]) {  // v * (1 / sqrt((x x + y y) + z z))
+        const float xx = see(v[0] * v[0]), yy = see(v[1] * v[1]), zz = see(v[2] * v[2]);
+        const float r = see(1.0f / see(std::sqrt(see(see(xx + yy) + zz))));
+        scaled(v, r, out);
+    }
+};
+
+}  // namespace
+
+std::vector<uint8_t> pack_surface_section(const ChosenTrees& trees, const PackedScene& packed, uint32_t stack_entries, size_t lds_limit) {
+    std::vector<uint8_t> section;
+    const hiprz_scene* sc = &trees.scene;
+    if (trees.own_trees || sc->n_instances == 0u || packed.hot_bytes() + size_t(stack_entries) * 1024u > lds_limit) return section;
+    // the triangles of a mesh: what the leaves under its root cover (the snapshot was validated: every tree ends)
+    struct Range {
+        uint32_t lo = RZ_END, hi = 0u;
+    };
+    std::vector<Range> range_of_root(sc->n_nodes);
+    std::vector<uint8_t> ranged(sc->n_nodes, 0);
+    const uint32_t table_words = (sc->n_instances + 3u) & ~3u;
+    std::vector<uint32_t> table(table_words, 0u);
+    std::vector<uint32_t> words;  // the records, 8 words each
+    std::vector<uint32_t> todo;
+    for (const uint32_t i : packed.world_members) {  // (an instance outside the world tree is never hit, and nobody validated its mesh tree)
+        const hiprz_instance& in = sc->instances[i];
+        const uint32_t root = in.blas_root;
+        if (!ranged[root]) {
+            Range r;
+            todo.assign(1, root);
+            while (!todo.empty()) {
+                const hiprz_node& n = sc->nodes[todo.back()];
+                todo.pop_back();
+                if (n.meta & HIPRZ_NODE_LEAF) {
+                    const uint32_t count = n.meta & HIPRZ_NODE_COUNT_MASK;
+                    if (count) r.lo = std::min(r.lo, n.begin), r.hi = std::max(r.hi, n.begin + count);
+                } else {
+                    todo.push_back(n.begin), todo.push_back(n.begin + 1u);
+                }
+            }
+            range_of_root[root] = r, ranged[root] = 1;
+        }
+        const Range r = range_of_root[root];
+        if (r.lo >= r.hi) continue;  // an empty mesh: never hit
+        table[i] = uint32_t(words.size() / 16u) - r.lo;  // (modulo 2^32, like the device's addition)
+        float scale_in[3];
+        SurfaceMath placement;
+        for (int a = 0; a < 3; ++a) scale_in[a] = placement.see(in.scale[a]), placement.see(in.x_axis[a]), placement.see(in.y_axis[a]), placement.see(in.z_axis[a]);
+        for (uint32_t t = r.lo; t < r.hi; ++t) {
+            const uint32_t flags = sc->tris[t].material_flags;
+            uint32_t slot = flags & HIPRZ_TRI_MATERIAL_MASK;
+            if (slot > 63u) slot = 63u;
+            int32_t mat = -1;
+            if (slot < in.material_count && uint64_t(in.material_base) + slot < sc->n_inst_materials) mat = sc->inst_materials[in.material_base + slot];
+            const uint32_t surface_material = mat < 0 ? HIPRZ_MATERIAL_DEFAULT : uint32_t(mat);
+            const float* face_normal = sc->tri_attrs[t].face_normal;
+            for (uint32_t external = 0; external < 2u; ++external) {
+                const float ef = float(external) * 2.0f - 1.0f;
+                SurfaceMath math = placement;
+                for (int a = 0; a < 3; ++a) math.see(face_normal[a]);
+                float v[3], w[3], normal[3], mapped[3];
+                math.scaled(face_normal, ef, v);   // sf.normal = normalized(transform_forward((face_normal * ef) / scale))
+                math.divided(v, scale_in, w);
+                math.forward(in, w, v);
+                math.normalize(v, normal);
+                math.divided(face_normal, scale_in, w);  // sf.mapped_normal = normalized(transform_forward(face_normal / scale)) * ef
+                math.forward(in, w, v);
+                math.normalize(v, w);
+                math.scaled(w, ef, mapped);
+                uint32_t valid = 0u;
+                if (!math.bad) valid = kSurfaceNormalValid | ((flags & HIPRZ_TRI_HAS_NORMALS) ? 0u : kSurfaceMappedValid);
+                uint32_t rec[8];
+                std::memcpy(rec, normal, 12), std::memcpy(rec + 4, mapped, 12);
+                rec[3] = surface_material, rec[7] = valid;
+                words.insert(words.end(), rec, rec + 8);
+            }
+        }
+    }
+    static_assert(kSurfaceRecordBytes == 32u, "two float4 per record");
+    section.resize(4u * (size_t(table_words) + words.size()));
+    std::memcpy(section.data(), table.data(), 4u * size_t(table_words));
+    if (!words.empty()) std::memcpy(section.data() + 4u * size_t(table_words), words.data(), 4u * words.size());
+    return section;
 }
 
 uint32_t enter_device_roots(std::vector<hiprz_instance>& instances, const std::vector<uint32_t>& instance_mesh, const std::vector<DeviceMesh>& meshes,

@@ -158,6 +158,30 @@ struct PackedScene {
 // `pair_records` = false leaves pair_section empty and everything else what it is with it (tests/test_pair_records.py compares the two).
 int pack_scene(const ChosenTrees& trees, DerivedTables&& derived, PackedScene& out, std::string& error, bool pair_records = true);
 
+// Surface records: what analyze_intersection (hiprz_device.hpp) derives from (instance, triangle, side hit) alone, computed once per
+// upload for the kernels that stage the scene in LDS (RZ_SURFACE_RECORDS).  NOT part of `blob` and NOT counted in hot_bytes(): the upload
+// places the section 16-byte aligned behind the hot buffer's hot_bytes(), nothing stages it (every LDS figure of the launch plan stays
+// what it is; one more byte of LDS costs config B its fifth workgroup per CU) and the kernels read it from global memory through
+// DScene::hot.  Layout: a table of ((n_instances + 3) & ~3) 32-bit words — instance id -> (index of its first record pair - first
+// triangle of its mesh), so the pair of a hit is table[instance] + hit.triangle —, then per (instance of the world tree, triangle of its mesh) two records
+// of kSurfaceRecordBytes, the side hit from inside (external = 0) first: normal.xyz, bits(surface_material), mapped_normal.xyz,
+// bits(flags).  behind_material follows from the side (external ? surface_material : HIPRZ_MATERIAL_WORLD).  A mesh's triangles are the
+// range [lowest, highest) its tree's leaves cover.
+// Every record is computed by analyze_intersection's literal sequence for ITS side — the slot clamp and the HIPRZ_MATERIAL_DEFAULT rule;
+// normalized(transform_forward((face_normal * ef) / scale)); normalized(transform_forward(face_normal / scale)) * ef — because the two
+// sides are not each other's negation: (+0) + (-0) is +0 under either sign, so an axis-aligned wall's zeros differ in sign between the
+// sides, and the sign reaches 1 / d of the next segment's slab tests.  Host and device agree bit for bit (-ffp-contract=off, no fast
+// math, correctly rounded division and square root on both) for finite, normal numbers only: kSurfaceNormalValid and
+// kSurfaceMappedValid are both clear when an input or an intermediate is subnormal, infinite or NaN (a zero-area triangle among them),
+// kSurfaceMappedValid also for a triangle with HIPRZ_TRI_HAS_NORMALS (its mapped normal is interpolated per hit); a lane that finds a
+// flag clear computes that normal as before.
+// Built for every scene that may be staged: the snapshot's own trees and hot_bytes() + stack_entries * 1 KiB <= lds_limit (the widest
+// rule of hiprz_plan.cpp: use_lds_scene); empty otherwise.  Such a scene's geometry and instances change through hiprz_upload_scene
+// alone (see pair_section), and hiprz_update_shading changes no material id, so the section cannot go stale.
+constexpr uint32_t kSurfaceRecordBytes = RZ_SURFACE_RECORD_BYTES;
+constexpr uint32_t kSurfaceNormalValid = RZ_SURFACE_NORMAL_VALID, kSurfaceMappedValid = RZ_SURFACE_MAPPED_VALID;
+std::vector<uint8_t> pack_surface_section(const ChosenTrees& trees, const PackedScene& packed, uint32_t stack_entries, size_t lds_limit);
+
 // Instances enter their mesh at the root the device built (where it built one); returns the nodes the builds emitted.
 uint32_t enter_device_roots(std::vector<hiprz_instance>& instances, const std::vector<uint32_t>& instance_mesh, const std::vector<DeviceMesh>& meshes,
                             uint32_t world_slots);
