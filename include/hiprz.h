@@ -688,6 +688,13 @@ int hiprz_selftest(hiprz_ctx* ctx, uint32_t cases_per_thread, uint32_t seed, uin
  * on the host that the result is a STABLE permutation in key order and that the sorted keys are the keys in that order.
  * *errors = violations found, *sort_us = device time of the fastest repeat (HIP events on the context's stream). */
 int hiprz_selftest_sort(hiprz_ctx* ctx, const uint32_t* keys_host, uint32_t n, int key_bits, uint32_t repeats, uint64_t* errors, double* sort_us);
+/* The same sort for a caller's DEVICE keys (include/hiprz_order.h sorts ray keys with it).  Host only, no kernel of its own, and it only
+ * enqueues, on `stream` (a hipStream_t; NULL = hiprz_stream(ctx)): keys_device holds n keys of 1..32 significant bits from bit 0 (the sort
+ * looks at whole bytes) and is DESTROYED; perm_out_device receives the STABLE permutation in key order — perm[i] is the index of the key
+ * that comes i-th, equal keys in the order they came in.  The ping-pong workspace is the context's own, apart from every frame's and grown
+ * on demand, so a render between two sorts does not see it; one such sort at a time per context.  HIPRZ_ERR_INVALID on a null pointer,
+ * key_bits outside 1..32 and n > 2^30; n == 0 is HIPRZ_OK without a launch. */
+int hiprz_sort_u32_device(hiprz_ctx* ctx, uint32_t* keys_device, uint32_t n, int key_bits, uint32_t* perm_out_device, void* stream);
 
 /* --- timing (TimeTable, engine_parts.hpp:34-74; Engine::debugInfo, rayzath.cpp:96-113) --- */
 int hiprz_timings(hiprz_ctx* ctx, char* buf, size_t len);

@@ -204,6 +204,7 @@ ENTRY_POINTS = {
     "hiprz_denoise_layout": (None, [P]),
     "hiprz_selftest": (C.c_int, [P, U32, U32, C.POINTER(U64), C.POINTER(U64)]),
     "hiprz_selftest_sort": (C.c_int, [P, C.POINTER(U32), U32, C.c_int, U32, C.POINTER(U64), C.POINTER(C.c_double)]),
+    "hiprz_sort_u32_device": (C.c_int, [P, P, U32, C.c_int, P, P]),
     "hiprz_timings": (C.c_int, [P, C.c_char_p, SZ]),
     "hiprz_time_kernels": (C.c_int, [P, C.c_int]),
     "hiprz_kernel_breakdown_ms": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(U32)]),

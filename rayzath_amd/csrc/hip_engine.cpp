@@ -347,6 +347,7 @@ Engine::Engine(const std::vector<int>& devices) : m_device(devices.empty() ? 0 :
 Engine::~Engine() {
     if (m_meter) hiprz_noise_destroy(m_meter);
     if (m_query) hiprz_query_destroy(m_query);
+    if (m_order) hiprz_order_destroy(m_order);
     hiprz_destroy(m_ctx);
 }
 
@@ -401,22 +402,40 @@ hiprz_query* Engine::query() {
     return m_query;
 }
 
-std::vector<hiprz_hit> Engine::castRays(const std::vector<hiprz_ray>& rays, bool normalize) {
+hiprz_order* Engine::order() {
+    if (!m_order)
+        if (const int rc = hiprz_order_create(&m_order, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_order_last_error(nullptr));
+    return m_order;
+}
+
+std::vector<hiprz_hit> Engine::castRays(const std::vector<hiprz_ray>& rays, bool normalize, bool ordered) {
     std::lock_guard<std::mutex> lock(m_mutex);
     std::vector<hiprz_hit> hits(rays.size());
     if (rays.empty()) return hits;
+    const uint32_t flags = normalize ? HIPRZ_QUERY_NORMALIZE : 0u;
+    if (ordered) {
+        hiprz_order* o = order();
+        if (const int rc = hiprz_order_closest_host(o, rays.data(), rays.size(), flags, hits.data()); rc != HIPRZ_OK) throw Exception(rc, hiprz_order_last_error(o));
+        return hits;
+    }
     hiprz_query* q = query();
-    const int rc = hiprz_query_closest_host(q, rays.data(), rays.size(), normalize ? HIPRZ_QUERY_NORMALIZE : 0u, hits.data());
+    const int rc = hiprz_query_closest_host(q, rays.data(), rays.size(), flags, hits.data());
     if (rc != HIPRZ_OK) throw Exception(rc, hiprz_query_last_error(q));
     return hits;
 }
 
-std::vector<uint32_t> Engine::occluded(const std::vector<hiprz_ray>& rays, bool normalize) {
+std::vector<uint32_t> Engine::occluded(const std::vector<hiprz_ray>& rays, bool normalize, bool ordered) {
     std::lock_guard<std::mutex> lock(m_mutex);
     std::vector<uint32_t> out(rays.size());
     if (rays.empty()) return out;
+    const uint32_t flags = normalize ? HIPRZ_QUERY_NORMALIZE : 0u;
+    if (ordered) {
+        hiprz_order* o = order();
+        if (const int rc = hiprz_order_occluded_host(o, rays.data(), rays.size(), flags, out.data()); rc != HIPRZ_OK) throw Exception(rc, hiprz_order_last_error(o));
+        return out;
+    }
     hiprz_query* q = query();
-    const int rc = hiprz_query_occluded_host(q, rays.data(), rays.size(), normalize ? HIPRZ_QUERY_NORMALIZE : 0u, out.data());
+    const int rc = hiprz_query_occluded_host(q, rays.data(), rays.size(), flags, out.data());
     if (rc != HIPRZ_OK) throw Exception(rc, hiprz_query_last_error(q));
     return out;
 }
@@ -491,6 +510,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
             if (hiprz_create_multi(&several, ids.data(), streams) == HIPRZ_OK) {
                 if (m_query) hiprz_query_destroy(m_query);  // bound to the context that goes
                 m_query = nullptr;
+                if (m_order) hiprz_order_destroy(m_order);
+                m_order = nullptr;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

@@ -24,6 +24,7 @@
 
 #include "hiprz.h"
 #include "hiprz_noise.h"
+#include "hiprz_order.h"
 #include "hiprz_query.h"
 
 namespace RayZath::Hip {
@@ -243,8 +244,10 @@ public:
     void noise(hiprz_noise_summary& out, float threshold = 1.0f / 255.0f, uint32_t min_batches = 8);
     // Ray queries (include/hiprz_query.h): the closest hit / the occlusion of every ray of `rays` in the world of the last renderWorld call,
     // in caller order; normalize: the device's normalized() is applied to the directions first.  Wait for the stream; change no frame.
-    std::vector<hiprz_hit> castRays(const std::vector<hiprz_ray>& rays, bool normalize = false);
-    std::vector<uint32_t> occluded(const std::vector<hiprz_ray>& rays, bool normalize = false);
+    // ordered: walked in the renderer's sorted ray order (include/hiprz_order.h) — the same bytes, sooner for a large batch of rays in no
+    // particular order, later for rays that arrive coherent.
+    std::vector<hiprz_hit> castRays(const std::vector<hiprz_ray>& rays, bool normalize = false, bool ordered = false);
+    std::vector<uint32_t> occluded(const std::vector<hiprz_ray>& rays, bool normalize = false, bool ordered = false);
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -289,6 +292,8 @@ private:
     hiprz_noise_meter* m_meter = nullptr;   // on the head device, created at the first measurement
     hiprz_query* m_query = nullptr;         // bound to m_ctx, created at the first query
     hiprz_query* query();
+    hiprz_order* m_order = nullptr;         // bound to m_ctx, created at the first ordered query
+    hiprz_order* order();
     int wantVariance() const { return m_measuring || (m_denoise && (m_denoise_params.flags & HIPRZ_DENOISE_VARIANCE)) ? 1 : 0; }
     std::mutex m_mutex;  // renderWorld is serialised (cpu_engine_core.cpp:15)
     bool m_pending_readback = false;

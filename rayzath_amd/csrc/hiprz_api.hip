@@ -855,6 +855,7 @@ int hiprz_destroy(hiprz_ctx* c) {
     c->world_items.release(), c->update_tris.release(), c->update_attrs.release();
     c->shadow_nodes64.release(), c->shadow_order.release();
     c->build_sort.keys_out.release(), c->build_sort.vals_a.release(), c->build_sort.vals_b.release(), c->build_sort.counts.release(), c->build_sort.row_total.release();
+    c->caller_sort.keys_out.release(), c->caller_sort.vals_a.release(), c->caller_sort.vals_b.release(), c->caller_sort.counts.release(), c->caller_sort.row_total.release();
     c->texels.release(), c->spot_lights.release(), c->direct_lights.release();
     release_present(c, c);
     release_frame(c);

@@ -257,6 +257,7 @@ struct hiprz_ctx : hiprz_frame_state {
     hiprz::DeviceArray<hiprz_tri> update_tris;
     hiprz::DeviceArray<hiprz_tri_attr> update_attrs;
     hiprz_frame_state::SortTemp build_sort;
+    hiprz_frame_state::SortTemp caller_sort;  // hiprz_sort_u32_device: a caller's sort never shares a frame's sort_temp[] (a render may run between two of them)
     hiprz::DeviceArray<uint32_t> shadow_nodes64, shadow_order;  // the shadow rays' own world tree (build_shadow_world_tree)
     std::vector<uint32_t> world_members;                         // the instances of the world tree (those with a mesh), by rising id
     std::vector<hiprz::DeviceMesh> device_meshes;

@@ -327,3 +327,20 @@ int hiprz_selftest_sort(hiprz_ctx* c, const uint32_t* keys_host, uint32_t n, int
     return HIPRZ_OK;
 }
 
+// hiprz.h: the sort for a caller's device keys, enqueue only.  The ping-pong buffers are the context's caller_sort — no frame's
+// sort_temp[], which a render between two of these calls uses — grown on demand (growing frees the old buffers, which waits for
+// whatever still uses them).
+int hiprz_sort_u32_device(hiprz_ctx* c, uint32_t* keys_device, uint32_t n, int key_bits, uint32_t* perm_out_device, void* stream) {
+    using namespace hiprz;
+    if (!c) return HIPRZ_ERR_INVALID;
+    if (!keys_device || !perm_out_device) return fail(c, HIPRZ_ERR_INVALID, "sort_u32_device: null pointer");
+    if (key_bits < 1 || key_bits > 32) return fail(c, HIPRZ_ERR_INVALID, "sort_u32_device: key_bits outside 1..32");
+    if (n > (1u << 30)) return fail(c, HIPRZ_ERR_INVALID, "sort_u32_device: more than 2^30 keys");
+    if (n == 0u) return HIPRZ_OK;
+    (void)hipSetDevice(c->device);
+    const int rc = sort_temp_resize(c, c->caller_sort, n);
+    if (rc != HIPRZ_OK) return rc;
+    sort_u32(stream ? static_cast<hipStream_t>(stream) : c->stream, keys_device, n, key_bits, perm_out_device, nullptr, c->caller_sort);
+    RZ_HIP(c, hipGetLastError());
+    return HIPRZ_OK;
+}

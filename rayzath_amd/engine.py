@@ -131,6 +131,9 @@ class Context:
         if getattr(self, "_query", None) is not None:
             self._query.close()
             self._query = None
+        if getattr(self, "_order", None) is not None:
+            self._order.close()
+            self._order = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -433,15 +436,30 @@ class Context:
             self._query = _query.Query(self._ctx)
         return self._query
 
-    def trace(self, rays, normalize=False):
+    def order(self):
+        """the context's order.Order (include/hiprz_order.h), created at the first use: the queries above walked in sorted ray order"""
+        from . import order as _order
+        if getattr(self, "_order", None) is None:
+            self._order = _order.Order(self._ctx)
+        return self._order
+
+    def trace(self, rays, normalize=False, ordered=False):
         """The closest hit of every ray of `rays` (an array of query.ray_dtype) in the uploaded world: an array of query.hit_dtype of the
         same shape.  normalize: the device's normalized() is applied to the directions first, t is then along the normalised direction;
-        otherwise the directions must be of unit length.  An invalid ray reads HIT_INVALID.  Waits for the stream; changes no frame."""
-        return self.query().closest(rays, normalize)
+        otherwise the directions must be of unit length.  An invalid ray reads HIT_INVALID.  Waits for the stream; changes no frame.
+        ordered: the rays are walked in the renderer's sorted order (include/hiprz_order.h) — the same bytes, sooner for a large batch of
+        rays in no particular order, later for rays that arrive coherent (a camera's pixels)."""
+        return (self.order() if ordered else self.query()).closest(rays, normalize)
 
-    def occluded(self, rays, normalize=False):
-        """uint32 per ray: 1 = some triangle lies within (near, far) of the ray.  Waits for the stream; changes no frame."""
-        return self.query().occluded(rays, normalize)
+    def occluded(self, rays, normalize=False, ordered=False):
+        """uint32 per ray: 1 = some triangle lies within (near, far) of the ray.  Waits for the stream; changes no frame.  ordered: as
+        for trace."""
+        return (self.order() if ordered else self.query()).occluded(rays, normalize)
+
+    def ray_order(self, rays, normalize=False):
+        """(perm, keys), uint32 arrays of rays.size: the order an ordered query walks `rays` in — perm[i] is the index (into the flattened
+        rays) of the ray walked i-th, the stable order of keys — and every ray's 24-bit sort key, 0 for an invalid ray"""
+        return self.order().permutation(rays, normalize, self.sync)
 
     def pixel_rays(self):
         """(H, W) array of query.ray_dtype: the selected camera's pixel-centre rays, the ones the first pass, the guides and ray_cast walk"""
