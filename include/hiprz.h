@@ -681,7 +681,11 @@ int hiprz_variance_device(hiprz_ctx* ctx, const void** out);
 int hiprz_accum_device(hiprz_ctx* ctx, const void** out);
 
 /* Device self-test of the kernels' exact-arithmetic shortcuts (shared-reciprocal division must
- * equal the correctly rounded quotient): runs 262144 * cases_per_thread random cases. */
+ * equal the correctly rounded quotient): runs 262144 * cases_per_thread random cases.  Every case also runs the glossy sampler's
+ * powf / acosf / sincosf sequence at roughness +0 and -0 on a draw in [0, 1) (every sixteenth on 0, 2^-24 or 1 - 2^-24): it must return
+ * (+0, 1), the constants sample_direction takes for a mirror; and every block compares the two-fma form of a byte over 255 with the
+ * division for all 256 bytes.  Both report into *mismatches only; *tested counts the quotients and filtered box tests, as before.
+ * hiprz_timings then carries, as a count, the cases in which roughness 2^-100 did not return the same (+0, 1). */
 int hiprz_selftest(hiprz_ctx* ctx, uint32_t cases_per_thread, uint32_t seed, uint64_t* mismatches, uint64_t* tested);
 /* Device self-test of the ray-order radix sort (hiprz_sort.hip; no reference counterpart — the reference traces pixels in tile order):
  * sorts the caller's n keys (host array, 1..32 significant bits from bit 0; the sort looks at whole bytes) `repeats` times and checks

@@ -59,10 +59,14 @@ __global__ void __launch_bounds__(256) rz_moments_kernel(const float4* accum, fl
 }
 
 // Device self-test: div_shared() must equal the correctly rounded `/` bit for bit over its
-// whole stated operand range.  out[0] = mismatches, out[1] = cases tested.
+// whole stated operand range.  out[0] = mismatches, out[1] = cases tested, out[2] = box tests the filter left undecided,
+// out[3] = lobe cases in which roughness 2^-100 does not return the mirror's (+0, 1).
 __global__ void __launch_bounds__(256) rz_selftest_div_kernel(uint32_t n_per_thread, uint32_t seed, unsigned long long* out) {
     uint32_t h = mix32(seed ^ (blockIdx.x * 256u + threadIdx.x) * 0x9E3779B9u);
-    uint32_t bad = 0, tested = 0, undecided = 0;
+    uint32_t bad = 0, tested = 0, undecided = 0, tiny_differs = 0;
+    // a byte over 255 (hiprz_u8_div.hpp, RZ_U8_SHORT_DIV): the two-fma form against the division, bit for bit, for every byte — thread
+    // t of each block takes byte t; called directly, whichever way the switch stands
+    if (__float_as_uint(u8_over_255_short(float(threadIdx.x))) != __float_as_uint(float(threadIdx.x) / 255.0f)) bad += 1;
     for (uint32_t i = 0; i < n_per_thread; ++i) {
         h = mix32(h + i);
         // d: random sign/mantissa, exponent in [-40, 2); n: zero or exponent in [-84, 41)
@@ -85,6 +89,29 @@ __global__ void __launch_bounds__(256) rz_selftest_div_kernel(uint32_t n_per_thr
         float sn, cs;
         sincosf(angle, &sn, &cs);
         if (__float_as_uint(sn) != __float_as_uint(sinf(angle)) || __float_as_uint(cs) != __float_as_uint(cosf(angle))) bad += 1;
+        // the glossy lobe of a mirror (RZ_MIRROR_LOBE_CONST, sample_direction): the general sequence — spelled here, so that it runs
+        // whichever way the switch stands — must return (sin, cos) = (+0, 1) at roughness +0 and -0 for every draw u2 in [0, 1); every
+        // sixteenth case takes an end of the range: 0, 2^-24, 1 - 2^-24.  Reports into `bad` only.  `tiny_differs` counts the cases in
+        // which roughness 2^-100 — a value that takes the general path under either setting — does not return the same bits:
+        // tests/test_mirror_lobe_gpu.py renders its twin worlds with it.
+        {
+            float u2 = float(mix32(h + 0x10BEu) >> 8) * (1.0f / 16777216.0f);
+            if ((i & 15u) == 15u) {
+                const uint32_t edge = (i >> 4) % 3u;
+                u2 = edge == 0u ? 0.0f : edge == 1u ? 1.0f / 16777216.0f : 1.0f - 1.0f / 16777216.0f;
+            }
+            auto lobe = [&](float roughness, float& s_xy, float& c_z) {
+                const float theta = RZ_ACOSF(1.0f - 2.0f * ((1.0f - RZ_POWF(u2 + 1.0e-5f, roughness)) * 0.5f));
+                RZ_SINCOSF(theta, s_xy, c_z);
+            };
+            // the roughness comes out of a register the compiler cannot fold: +0 or -0 by a bit of the hash, the other sign second
+            const float zero = __uint_as_float(h & 0x80000000u), other = __uint_as_float(~h & 0x80000000u);
+            float s0, c0, s1, c1, st, ct;
+            lobe(zero, s0, c0), lobe(other, s1, c1), lobe(__uint_as_float((127u - 100u) << 23), st, ct);
+            if (__float_as_uint(s0) != 0x00000000u || __float_as_uint(c0) != 0x3F800000u) bad += 1;
+            if (__float_as_uint(s1) != 0x00000000u || __float_as_uint(c1) != 0x3F800000u) bad += 1;
+            if (__float_as_uint(st) != 0x00000000u || __float_as_uint(ct) != 0x3F800000u) tiny_differs += 1;
+        }
         // the filtered box test (box_filter): whenever it claims to know, the exact test must agree.  A ray from a random point towards a
         // random direction against a random box around the origin region — every second case with a face of the box exactly ON the ray's
         // range end or through the ray's origin plane, where comparisons are decided by a rounding
@@ -213,6 +240,7 @@ __global__ void __launch_bounds__(256) rz_selftest_div_kernel(uint32_t n_per_thr
     atomicAdd(&out[0], (unsigned long long)bad);
     atomicAdd(&out[1], (unsigned long long)tested);
     atomicAdd(&out[2], (unsigned long long)undecided);
+    atomicAdd(&out[3], (unsigned long long)tiny_differs);
 }
 
 // =======================================================================================
@@ -1223,12 +1251,14 @@ int hiprz_selftest(hiprz_ctx* c, uint32_t cases_per_thread, uint32_t seed, uint6
     (void)hipSetDevice(c->device);
     RZ_HIP(c, hipMemsetAsync(c->counters_dev.ptr, 0, 8 * sizeof(unsigned long long), c->stream));
     RZ_LAUNCH(rz_selftest_div_kernel, dim3(1024), dim3(256), 0, c->stream, cases_per_thread, seed, c->counters_dev.ptr);
-    unsigned long long v[3];
+    unsigned long long v[4];
     RZ_HIP(c, hipMemcpyAsync(v, c->counters_dev.ptr, sizeof v, hipMemcpyDeviceToHost, c->stream));
     RZ_HIP(c, hipStreamSynchronize(c->stream));
     *mismatches = v[0], *tested = v[1];
     // how often the filtered box test has to fall back to the exact sequence on these (adversarial: half of them put a face on a range end) cases
     c->timings.set("selftest: box tests the filter left undecided, per million", double(v[2]) * 1.0e6 / double(262144ull * cases_per_thread));
+    // a count, not a time: 0 = a material of roughness 2^-100 samples the direction a mirror does, through the general sequence
+    c->timings.set("selftest: lobe cases where roughness 2^-100 leaves (+0, 1)", double(v[3]));
     return HIPRZ_OK;
 }
 

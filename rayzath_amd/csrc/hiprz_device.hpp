@@ -19,6 +19,7 @@
 #define RZ_DEV __device__ __forceinline__
 #include "hiprz_flat_pick.hpp"
 #include "hiprz_pair_pick.hpp"
+#include "hiprz_u8_div.hpp"
 
 namespace hiprz {
 
@@ -43,6 +44,9 @@ namespace hiprz {
 #endif
 #ifndef RZ_FLAT_PK_DIV         // ... and tri_hit2's two true divisions as ONE sequence, its six plain operations packed (rcp_pair)
 #define RZ_FLAT_PK_DIV 0       // off: on top of the records it takes 0.5 % back, alone the five-wave build spills inside the walk (-17.7 %)
+#endif
+#ifndef RZ_MIRROR_LOBE_CONST   // sample_direction: a glossy lobe of roughness +-0 takes (sin, cos) = (+0, 1), the constants its powf, acosf and sincosf return
+#define RZ_MIRROR_LOBE_CONST 1
 #endif
 #ifndef RZ_TRACE_MIN_WAVES
 #define RZ_TRACE_MIN_WAVES 5
@@ -237,8 +241,8 @@ RZ_DEV float similarity(v3 a, v3 b) { return dot(a, b) * (rcp_magnitude(a) * rcp
 
 RZ_DEV col4 splat(float v) { return col4{v, v, v, v}; }
 RZ_DEV col4 from_u8(uint32_t rgba) {
-    return col4{float(rgba & 255u) / 255.0f, float((rgba >> 8) & 255u) / 255.0f, float((rgba >> 16) & 255u) / 255.0f,
-                float(rgba >> 24) / 255.0f};
+    return col4{u8_over_255(float(rgba & 255u)), u8_over_255(float((rgba >> 8) & 255u)), u8_over_255(float((rgba >> 16) & 255u)),
+                u8_over_255(float(rgba >> 24))};
 }
 RZ_DEV col4 operator+(col4 a, col4 b) { return col4{a.r + b.r, a.g + b.g, a.b + b.b, a.a + b.a}; }
 RZ_DEV col4 operator-(col4 a, col4 b) { return col4{a.r - b.r, a.g - b.g, a.b - b.b, a.a - b.a}; }
@@ -429,7 +433,7 @@ RZ_DEV bool zero_or_exponent_in(float x, int lo, int hi) {
     return (__float_as_uint(x) & 0x7FFFFFFFu) == 0u || exponent_in(x, lo, hi);
 }
 #ifdef RZ_PHASE_STATS  // diagnostic build: wave-level executions and active lanes of the MODE 3 walk's steps (tools/phase_stats.py)
-static __device__ unsigned long long rz_phase[16];  // one copy per translation unit: read through that unit's hiprz_read_phase_stats
+static __device__ unsigned long long rz_phase[32];  // one copy per translation unit: read through that unit's hiprz_read_phase_stats
 #define RZ_PHASE(k)                                                                                        \
     do {                                                                                                   \
         const unsigned long long rz_a = __ballot(1);                                                       \
@@ -2409,7 +2413,7 @@ RZ_DEV col4 fetch_rgba8(const DScene& s, int32_t tex, float u, float v, Counters
 }
 template <bool COUNT>
 RZ_DEV float fetch_r8(const DScene& s, int32_t tex, float u, float v, Counters& cnt) {
-    return float(s.texels[texel_offset<COUNT>(s, tex, u, v, 1u, cnt)]) / 255.0f;
+    return u8_over_255(float(s.texels[texel_offset<COUNT>(s, tex, u, v, 1u, cnt)]));
 }
 template <bool COUNT>
 RZ_DEV float fetch_r32f(const DScene& s, int32_t tex, float u, float v, Counters& cnt) {
@@ -2654,8 +2658,20 @@ RZ_DEV v3 sample_direction(v3 ray_d, uint32_t& ray_material, Surface& sf, Rng& r
     if (diffuse) {
         s_xy = sqrtf(u2), c_z = sqrtf(1.0f - u2);
     } else {
-        const float theta = RZ_ACOSF(1.0f - 2.0f * ((1.0f - RZ_POWF(u2 + 1.0e-5f, sf.roughness)) * 0.5f));
-        RZ_SINCOSF(theta, s_xy, c_z);
+        RZ_PHASE(7);
+#if RZ_MIRROR_LOBE_CONST
+        // roughness +-0: powf(x, +-0) = 1, (1 - 1) * 0.5 = +0, 1 - 2 * 0 = 1, acosf(1) = +0, sincosf(+0) = (+0, 1) — the constants the
+        // sequence below returns (hiprz_selftest runs it on the device at both zeros); a wave whose glossy lanes are all mirrors skips it
+        if (sf.roughness == 0.0f) {
+            s_xy = 0.0f;
+            c_z = 1.0f;
+        } else
+#endif
+        {
+            RZ_PHASE(8);
+            const float theta = RZ_ACOSF(1.0f - 2.0f * ((1.0f - RZ_POWF(u2 + 1.0e-5f, sf.roughness)) * 0.5f));
+            RZ_SINCOSF(theta, s_xy, c_z);
+        }
     }
     v3 vX, vY;
     local_coordinate(sf.mapped_normal, vX, vY);

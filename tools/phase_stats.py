@@ -8,6 +8,9 @@ from rayzath_amd.engine import Context, RenderConfig, Tracing
 from rayzath_amd.scene import camera_struct, flatten
 NAMES = ["world node box test", "instance box test", "instance entry (to local)", "mesh node box test", "triangle test", "mesh walk round",
          "round on one lane per visit"]   # (the one-leaf binned walk: a round whose octets would not fit the workgroup)
+# sample_direction (counted in the unit of the kernel that shades — the split pipeline's shade kernel here): the merged sampler's glossy
+# branch, and inside it the powf / acosf / sincosf sequence (RZ_MIRROR_LOBE_CONST: lanes of roughness +-0 take constants instead)
+LOBE_NAMES = {7: "lobe sampler entered", 8: "general glossy sequence"}
 for cfgname in sys.argv[1:] or ["D"]:
     preset = scenes.CONFIGS[cfgname]
     w = preset["build"]()
@@ -18,14 +21,20 @@ for cfgname in sys.argv[1:] or ["D"]:
         ctx.set_traversal_mode(3), ctx.set_pipeline(1), ctx.set_ray_sort(int(os.environ.get('PHASE_RAY_SORT', '0')))
     ctx.set_tree(int(os.environ.get('PHASE_TREE', '4')))   # 4: the Engine hosts' default trees
     ctx.upload_scene(flatten(w)); ctx.upload_camera(camera_struct(w.camera)); ctx.set_config(RenderConfig(tracing=Tracing(preset["max_depth"], 8)).struct())
-    out = (C.c_uint64 * 16)()
+    out = (C.c_uint64 * 32)()
     ctx.render(9); ctx.sync(); ctx.lib.hiprz_read_phase_stats(out)
+    if hasattr(ctx.lib, "hiprz_read_shadow_phase_stats"): ctx.lib.hiprz_read_shadow_phase_stats(out)
     ctx.render(1); ctx.sync(); ctx.lib.hiprz_read_phase_stats(out)
     waves = ((w.camera.width + 31) // 32) * ((w.camera.height + 7) // 8) * 4
     print(f"config {cfgname}: one pass, {waves} waves")
     for k, name in enumerate(NAMES):
         n, lanes = out[2 * k], out[2 * k + 1]
         print(f"  {name:28s} wave executions {n:12d} ({n / waves:8.1f} per wave)  lanes {lanes:13d}  mean active lanes {lanes / max(n, 1):5.1f}")
+    if hasattr(ctx.lib, "hiprz_read_shadow_phase_stats"):   # the shade unit's counters of the SAME pass (read and cleared)
+        ctx.lib.hiprz_read_shadow_phase_stats(out)
+        for k, name in LOBE_NAMES.items():
+            n, lanes = out[2 * k], out[2 * k + 1]
+            print(f"  {name:28s} wave executions {n:12d} ({n / waves:8.3f} per wave)  lanes {lanes:13d}  mean active lanes {lanes / max(n, 1):5.1f}")
     if hasattr(ctx.lib, "hiprz_read_shadow_phase_stats") and os.environ.get("PHASE_SHADOW"):   # library built with -DRZ_PHASE_STATS in the shade unit too
         ctx.lib.hiprz_read_shadow_phase_stats(out); ctx.render(1); ctx.sync(); ctx.lib.hiprz_read_shadow_phase_stats(out)
         print("  shadow rays, wave-level walk (any_hit_packet):")
