@@ -692,6 +692,56 @@ int hiprz_selftest(hiprz_ctx* ctx, uint32_t cases_per_thread, uint32_t seed, uin
  * on the host that the result is a STABLE permutation in key order and that the sorted keys are the keys in that order.
  * *errors = violations found, *sort_us = device time of the fastest repeat (HIP events on the context's stream). */
 int hiprz_selftest_sort(hiprz_ctx* ctx, const uint32_t* keys_host, uint32_t n, int key_bits, uint32_t repeats, uint64_t* errors, double* sort_us);
+/* Device self-test of the shading arithmetic of hiprz_device.hpp, one function call per case (tests/test_device_math_gpu.py holds the
+ * results to float64 references): the library calls behind the RZ_* macros and the composed primitives, called themselves — what the
+ * render kernels inline — by one thread per case of rz_selftest_math_kernel.  `in` and `out` are HOST arrays of n_cases rows,
+ * floats_per_case_in and floats_per_case_out floats wide; the row layouts (uint32 fields travel as float bit patterns):
+ *   SINF COSF ACOSF ASINF EXPF LOGF SQRTF  x -> f(x)                 SINCOSF  x -> sin, cos
+ *   ATAN2F  y, x -> atan2f(y, x)     POWF  x, y -> powf(x, y)        DIV  a, b -> a / b
+ *   WRAP  u -> fmodf(fmodf(u, 1.0f) + 1.0f, 1.0f), the texture fetch's wrap
+ *   LOCAL_COORDINATE  n[3] -> vX[3], vY[3]
+ *   COSINE_SAMPLE_HEMISPHERE SAMPLE_SPHERE SAMPLE_HEMISPHERE  r1, r2, n[3] -> v[3]        SAMPLE_DISK  r1, r2, n[3], radius -> v[3]
+ *   FRESNEL  n[3], i[3], n1, n2, fx0, fy0 -> ratio, fx, fy   (the factors preset to fx0, fy0: total reflection leaves them untouched)
+ *   NDF  n[3], h[3], roughness -> ndf      ATTENUATION  cos_angle, roughness -> attenuation
+ *   REFLECT_VECTOR  i[3], n[3] -> v[3]     HALFWAY_VECTOR  i[3], r[3] -> v[3]
+ *   GLOSSY_LOBE  u2, roughness -> (sin, cos) of the reference's powf / acosf / sincosf sequence, (sin, cos) as sample_direction takes them
+ *   SAMPLE_DIRECTION  rng sx, sy, r; colour alpha, scattering, fresnel, reflectance, metalness, roughness; normal[3]; mapped normal[3];
+ *       refraction factors x, y; incoming direction[3]; ray material, behind material
+ *     -> twice (first sample_direction, then the reference's formulas spelled with the separate functions — cosine_sample_hemisphere;
+ *        sample_hemisphere and reflect_vector — on a copy of the same generator): direction[3], tint_factor, ray material, normal[3],
+ *        generator state a, b; then the path of the second spelling: 0 scattering, 1 refraction, 2 specular reflection, 3 diffuse,
+ *        4 glossy, plus 8 where the direction was flipped above the surface.
+ * HIPRZ_ERR_INVALID on a null pointer, an unknown op, row widths that are not the op's, or more than 2^24 cases; n_cases == 0 is HIPRZ_OK
+ * without a launch.  Waits for the stream; changes no frame. */
+#define HIPRZ_MATH_SINF 0u
+#define HIPRZ_MATH_COSF 1u
+#define HIPRZ_MATH_SINCOSF 2u
+#define HIPRZ_MATH_ACOSF 3u
+#define HIPRZ_MATH_ASINF 4u
+#define HIPRZ_MATH_ATAN2F 5u
+#define HIPRZ_MATH_POWF 6u
+#define HIPRZ_MATH_EXPF 7u
+#define HIPRZ_MATH_LOGF 8u
+#define HIPRZ_MATH_SQRTF 9u
+#define HIPRZ_MATH_DIV 10u
+#define HIPRZ_MATH_WRAP 11u
+#define HIPRZ_MATH_LOCAL_COORDINATE 12u
+#define HIPRZ_MATH_COSINE_SAMPLE_HEMISPHERE 13u
+#define HIPRZ_MATH_SAMPLE_SPHERE 14u
+#define HIPRZ_MATH_SAMPLE_HEMISPHERE 15u
+#define HIPRZ_MATH_SAMPLE_DISK 16u
+#define HIPRZ_MATH_FRESNEL 17u
+#define HIPRZ_MATH_NDF 18u
+#define HIPRZ_MATH_ATTENUATION 19u
+#define HIPRZ_MATH_REFLECT_VECTOR 20u
+#define HIPRZ_MATH_HALFWAY_VECTOR 21u
+#define HIPRZ_MATH_GLOSSY_LOBE 22u
+#define HIPRZ_MATH_SAMPLE_DIRECTION 23u
+#define HIPRZ_MATH_OP_COUNT 24u
+int hiprz_selftest_math(hiprz_ctx* ctx, uint32_t op, const float* in, uint32_t floats_per_case_in, uint32_t n_cases, float* out,
+                        uint32_t floats_per_case_out);
+/* Host only: the row widths of an op; HIPRZ_ERR_INVALID (nothing written) on an unknown op or a null pointer. */
+int hiprz_selftest_math_widths(uint32_t op, uint32_t* floats_per_case_in, uint32_t* floats_per_case_out);
 /* The same sort for a caller's DEVICE keys (include/hiprz_order.h sorts ray keys with it).  Host only, no kernel of its own, and it only
  * enqueues, on `stream` (a hipStream_t; NULL = hiprz_stream(ctx)): keys_device holds n keys of 1..32 significant bits from bit 0 (the sort
  * looks at whole bytes) and is DESTROYED; perm_out_device receives the STABLE permutation in key order — perm[i] is the index of the key

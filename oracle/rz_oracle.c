@@ -1042,6 +1042,17 @@ void rzo_sample_disk(float r1, float r2, const float n[3], float radius, float o
     v3 r = sample_disk(r1, r2, v3_from(n), radius);
     out[0] = r.x, out[1] = r.y, out[2] = r.z;
 }
+void rzo_sample_hemisphere(float r1, float r2, const float n[3], float out[3]) {
+    v3 r = sample_hemisphere(r1, r2, v3_from(n));
+    out[0] = r.x, out[1] = r.y, out[2] = r.z;
+}
+/* (sin, cos) of the glossy lobe's polar angle for the draw u2: what sampleGlossyDirection (cpu_engine_kernel.cpp:636-654) hands
+ * sample_hemisphere (:120-126) and sample_sphere (:102-119) makes of it */
+void rzo_glossy_lobe(float u2, float roughness, float out[2]) {
+    const float r2 = (1.0f - RZ_POWF(u2 + 1.0e-5f, roughness)) * 0.5f;
+    const float theta = RZ_ACOSF(1.0f - 2.0f * r2);
+    out[0] = RZ_SINF(theta), out[1] = RZ_COSF(theta);
+}
 
 /* ------------------------------------------------------------------------------------
  * BRDF — cpu_engine_kernel.cpp:556-594

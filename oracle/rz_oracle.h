@@ -118,6 +118,9 @@ float rzo_fresnel(const float n[3], const float i[3], float n1, float n2, float 
 void rzo_cosine_sample_hemisphere(float r1, float r2, const float n[3], float out[3]);
 void rzo_sample_sphere(float r1, float r2, const float n[3], float out[3]);
 void rzo_sample_disk(float r1, float r2, const float n[3], float radius, float out[3]);
+void rzo_sample_hemisphere(float r1, float r2, const float n[3], float out[3]);
+/* (sin, cos) of the glossy lobe's polar angle for the draw u2 at `roughness` (sampleGlossyDirection -> sample_hemisphere -> sample_sphere) */
+void rzo_glossy_lobe(float u2, float roughness, float out[2]);
 void rzo_tonemap_pixel(const float rgba[4], float aperture, float exposure_time, uint8_t out[4]);
 
 /* TextureBuffer::fetch of the CUDA engine (cuda_buffer.cuh:427-438) on scene->textures[texture], with its

@@ -204,6 +204,8 @@ ENTRY_POINTS = {
     "hiprz_denoise_layout": (None, [P]),
     "hiprz_selftest": (C.c_int, [P, U32, U32, C.POINTER(U64), C.POINTER(U64)]),
     "hiprz_selftest_sort": (C.c_int, [P, C.POINTER(U32), U32, C.c_int, U32, C.POINTER(U64), C.POINTER(C.c_double)]),
+    "hiprz_selftest_math": (C.c_int, [P, U32, P, U32, U32, P, U32]),
+    "hiprz_selftest_math_widths": (C.c_int, [U32, C.POINTER(U32), C.POINTER(U32)]),
     "hiprz_sort_u32_device": (C.c_int, [P, P, U32, C.c_int, P, P]),
     "hiprz_timings": (C.c_int, [P, C.c_char_p, SZ]),
     "hiprz_time_kernels": (C.c_int, [P, C.c_int]),
@@ -219,6 +221,12 @@ ENTRY_POINTS = {
     "hiprz_version": (C.c_char_p, []),
     "hiprz_kernel_count": (U32, []),
 }
+
+
+# hiprz_selftest_math: the ops by their HIPRZ_MATH_* value (include/hiprz.h holds the row layouts)
+MATH_OPS = ("sinf", "cosf", "sincosf", "acosf", "asinf", "atan2f", "powf", "expf", "logf", "sqrtf", "div", "wrap", "local_coordinate",
+            "cosine_sample_hemisphere", "sample_sphere", "sample_hemisphere", "sample_disk", "fresnel", "ndf", "attenuation",
+            "reflect_vector", "halfway_vector", "glossy_lobe", "sample_direction")
 
 
 def bind(lib):

@@ -2625,6 +2625,23 @@ RZ_DEV float brdf(v3 ray_d, const Surface& sf, v3 vPL) {
 RZ_DEV col4 brdf_color(const Surface& sf) { return lerp(sf.color, splat(1.0f), sf.reflectance); }
 
 // --- direction sampling: cpu_engine_kernel.cpp:596-687 ----------------------------------
+// (sin, cos) of the glossy lobe's polar angle for the draw u2 (sampleGlossyDirection :636-654 through sample_hemisphere and sample_sphere,
+// cpu_render_utils.cpp:102-126).  A function of its own so that hiprz_selftest_math evaluates what sample_direction inlines.
+RZ_DEV void glossy_lobe(float u2, float roughness, float& s_xy, float& c_z) {
+#if RZ_MIRROR_LOBE_CONST
+    // roughness +-0: powf(x, +-0) = 1, (1 - 1) * 0.5 = +0, 1 - 2 * 0 = 1, acosf(1) = +0, sincosf(+0) = (+0, 1) — the constants the
+    // sequence below returns (hiprz_selftest runs it on the device at both zeros); a wave whose glossy lanes are all mirrors skips it
+    if (roughness == 0.0f) {
+        s_xy = 0.0f;
+        c_z = 1.0f;
+    } else
+#endif
+    {
+        RZ_PHASE(8);
+        const float theta = RZ_ACOSF(1.0f - 2.0f * ((1.0f - RZ_POWF(u2 + 1.0e-5f, roughness)) * 0.5f));
+        RZ_SINCOSF(theta, s_xy, c_z);
+    }
+}
 RZ_DEV v3 sample_direction(v3 ray_d, uint32_t& ray_material, Surface& sf, Rng& rng) {
     if (sf.color.a > 0.0f) {
         if (sf.surface_scattering > 0.0f) {
@@ -2659,19 +2676,7 @@ RZ_DEV v3 sample_direction(v3 ray_d, uint32_t& ray_material, Surface& sf, Rng& r
         s_xy = sqrtf(u2), c_z = sqrtf(1.0f - u2);
     } else {
         RZ_PHASE(7);
-#if RZ_MIRROR_LOBE_CONST
-        // roughness +-0: powf(x, +-0) = 1, (1 - 1) * 0.5 = +0, 1 - 2 * 0 = 1, acosf(1) = +0, sincosf(+0) = (+0, 1) — the constants the
-        // sequence below returns (hiprz_selftest runs it on the device at both zeros); a wave whose glossy lanes are all mirrors skips it
-        if (sf.roughness == 0.0f) {
-            s_xy = 0.0f;
-            c_z = 1.0f;
-        } else
-#endif
-        {
-            RZ_PHASE(8);
-            const float theta = RZ_ACOSF(1.0f - 2.0f * ((1.0f - RZ_POWF(u2 + 1.0e-5f, sf.roughness)) * 0.5f));
-            RZ_SINCOSF(theta, s_xy, c_z);
-        }
+        glossy_lobe(u2, sf.roughness, s_xy, c_z);
     }
     v3 vX, vY;
     local_coordinate(sf.mapped_normal, vX, vY);

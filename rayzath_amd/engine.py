@@ -488,6 +488,23 @@ class Context:
                                                  C.byref(bad), C.byref(us)))
         return bad.value, us.value
 
+    def selftest_math(self, op, inputs):
+        """hiprz_selftest_math: one call of the device's shading arithmetic per row of `inputs`.  `op`: a name of _abi.MATH_OPS or its
+        HIPRZ_MATH_* value; `inputs`: float32, (n, width) or (n,) for an op of one argument (uint32 fields as float bit patterns; the row
+        layouts are in include/hiprz.h).  Returns the (n, width_out) float32 results."""
+        from . import _abi
+        op = _abi.MATH_OPS.index(op) if isinstance(op, str) else int(op)
+        w_in, w_out = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.hiprz_selftest_math_widths(op, C.byref(w_in), C.byref(w_out)))
+        inputs = np.ascontiguousarray(inputs, dtype=np.float32)
+        if inputs.ndim == 1:
+            inputs = inputs.reshape(-1, 1)
+        if inputs.ndim != 2 or inputs.shape[1] != w_in.value:
+            raise ValueError(f"op {op} takes rows of {w_in.value} floats, got an array of shape {inputs.shape}")
+        out = np.zeros((inputs.shape[0], w_out.value), dtype=np.float32)
+        self._check(self.lib.hiprz_selftest_math(self._ctx, op, inputs.ctypes.data, w_in.value, inputs.shape[0], out.ctypes.data, w_out.value))
+        return out
+
     def timings(self):
         buf = C.create_string_buffer(4096)
         self._check(self.lib.hiprz_timings(self._ctx, buf, len(buf)))

@@ -69,6 +69,8 @@ def load(path=LIB_PATH):
     lib.rzo_cosine_sample_hemisphere.restype, lib.rzo_cosine_sample_hemisphere.argtypes = None, [F, F, P, P]
     lib.rzo_sample_sphere.restype, lib.rzo_sample_sphere.argtypes = None, [F, F, P, P]
     lib.rzo_sample_disk.restype, lib.rzo_sample_disk.argtypes = None, [F, F, P, F, P]
+    lib.rzo_sample_hemisphere.restype, lib.rzo_sample_hemisphere.argtypes = None, [F, F, P, P]
+    lib.rzo_glossy_lobe.restype, lib.rzo_glossy_lobe.argtypes = None, [F, F, P]
     lib.rzo_tonemap_pixel.restype, lib.rzo_tonemap_pixel.argtypes = None, [P, F, F, P]
     lib.rzo_math_mode.restype, lib.rzo_math_mode.argtypes = C.c_char_p, []
     if path == LIB_PATH:
