@@ -348,6 +348,7 @@ Engine::~Engine() {
     if (m_meter) hiprz_noise_destroy(m_meter);
     if (m_query) hiprz_query_destroy(m_query);
     if (m_order) hiprz_order_destroy(m_order);
+    if (m_bake) hiprz_bake_destroy(m_bake);
     hiprz_destroy(m_ctx);
 }
 
@@ -440,6 +441,22 @@ std::vector<uint32_t> Engine::occluded(const std::vector<hiprz_ray>& rays, bool 
     return out;
 }
 
+std::vector<hiprz_bake_texel> Engine::bakeOcclusion(const std::vector<hiprz_bake_point>& points, uint32_t K, uint32_t S, uint32_t seed) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (!m_bake)
+        if (const int rc = hiprz_bake_create(&m_bake, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_bake_last_error(nullptr));
+    if (K != m_bake_k || S != m_bake_s) {  // the cosine table of (K, S), kept until another is asked for
+        std::vector<float> table(4 * size_t(K) * S);
+        if (const int rc = hiprz_bake_cosine_directions(K, S, table.data()); rc != HIPRZ_OK) throw Exception(rc, "bakeOcclusion: K is not one of 16 .. 1024 (powers of two) or S is not in 1..64");
+        if (const int rc = hiprz_bake_set_directions(m_bake, table.data(), K, S); rc != HIPRZ_OK) throw Exception(rc, hiprz_bake_last_error(m_bake));
+        m_bake_k = K, m_bake_s = S;
+    }
+    std::vector<hiprz_bake_texel> out(points.size());
+    if (points.empty()) return out;
+    if (const int rc = hiprz_bake_occlusion_host(m_bake, points.data(), points.size(), seed, out.data()); rc != HIPRZ_OK) throw Exception(rc, hiprz_bake_last_error(m_bake));
+    return out;
+}
+
 Engine::NoiseResult Engine::renderUntil(World& world, const RenderConfig& cfg, float target, uint32_t max_passes, uint32_t min_batches) {
     if (max_passes < 1u || min_batches < 2u) throw Exception(HIPRZ_ERR_INVALID, "renderUntil: max_passes must be at least 1 and min_batches at least 2");
     setMeasuring(true);
@@ -512,6 +529,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_query = nullptr;
                 if (m_order) hiprz_order_destroy(m_order);
                 m_order = nullptr;
+                if (m_bake) hiprz_bake_destroy(m_bake);
+                m_bake = nullptr, m_bake_k = m_bake_s = 0;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

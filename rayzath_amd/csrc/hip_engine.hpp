@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "hiprz.h"
+#include "hiprz_bake.h"
 #include "hiprz_noise.h"
 #include "hiprz_order.h"
 #include "hiprz_query.h"
@@ -248,6 +249,10 @@ public:
     // particular order, later for rays that arrive coherent.
     std::vector<hiprz_hit> castRays(const std::vector<hiprz_ray>& rays, bool normalize = false, bool ordered = false);
     std::vector<uint32_t> occluded(const std::vector<hiprz_ray>& rays, bool normalize = false, bool ordered = false);
+    // Occlusion baking (include/hiprz_bake.h): per surface point of `points`, how many of K rays of the cosine table (K, S) are occluded in
+    // the world of the last renderWorld call and the sum of the directions that are not; the rays are made and counted on the device.
+    // Waits for the stream; changes no frame.
+    std::vector<hiprz_bake_texel> bakeOcclusion(const std::vector<hiprz_bake_point>& points, uint32_t K = 64, uint32_t S = 4, uint32_t seed = 0);
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -294,6 +299,8 @@ private:
     hiprz_query* query();
     hiprz_order* m_order = nullptr;         // bound to m_ctx, created at the first ordered query
     hiprz_order* order();
+    hiprz_bake* m_bake = nullptr;           // bound to m_ctx, created at the first bake; it holds the cosine table of (m_bake_k, m_bake_s)
+    uint32_t m_bake_k = 0, m_bake_s = 0;
     int wantVariance() const { return m_measuring || (m_denoise && (m_denoise_params.flags & HIPRZ_DENOISE_VARIANCE)) ? 1 : 0; }
     std::mutex m_mutex;  // renderWorld is serialised (cpu_engine_core.cpp:15)
     bool m_pending_readback = false;

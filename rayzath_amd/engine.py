@@ -134,6 +134,9 @@ class Context:
         if getattr(self, "_order", None) is not None:
             self._order.close()
             self._order = None
+        if getattr(self, "_bake", None) is not None:
+            self._bake.close()
+            self._bake = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -460,6 +463,33 @@ class Context:
         """(perm, keys), uint32 arrays of rays.size: the order an ordered query walks `rays` in — perm[i] is the index (into the flattened
         rays) of the ray walked i-th, the stable order of keys — and every ray's 24-bit sort key, 0 for an invalid ray"""
         return self.order().permutation(rays, normalize, self.sync)
+
+    # --- occlusion baking: the rays of surface points made, walked and counted on the device (include/hiprz_bake.h) ---
+    def bake(self):
+        """the context's bake.Bake, created at the first use (device-pointer calls: occlusion_device, rays_device)"""
+        from . import bake as _bake
+        if getattr(self, "_bake", None) is None:
+            self._bake = _bake.Bake(self._ctx)
+        return self._bake
+
+    def _bake_with(self, directions):
+        b = self.bake()
+        if directions is not None and not (isinstance(directions, tuple) and directions == b.table):       # a cosine table already set is not set again
+            b.set_directions(directions)
+        return b
+
+    def bake_occlusion(self, points, directions=(64, 4), seed=0):
+        """Ambient occlusion of every surface point of `points` (an array of bake.point_dtype: position, near, normal, far) in the uploaded
+        world: an array of bake.texel_dtype of the same shape — `occluded` of the K rays of the point are occluded (bake.INVALID for an
+        invalid point), `bent` is the sum of the directions that are not.  directions: a (K, S) pair for the cosine table of S sets of K
+        directions, an (S, K, 4) float32 array of unit vectors around +z, or None for the table set before.  Point i uses set
+        bake.set_of(i, seed, S).  Waits for the stream; changes no frame."""
+        return self._bake_with(directions).occlusion(points, seed)
+
+    def bake_rays(self, points, seed=0, directions=None):
+        """The rays bake_occlusion walks for `points` under the table set before (or `directions`): query.ray_dtype of shape
+        points.shape + (K,), to feed to trace / occluded (closest-hit distances for distance-weighted occlusion)."""
+        return self._bake_with(directions).rays(points, seed, self.sync)
 
     def pixel_rays(self):
         """(H, W) array of query.ray_dtype: the selected camera's pixel-centre rays, the ones the first pass, the guides and ray_cast walk"""
