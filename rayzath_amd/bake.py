@@ -2,18 +2,14 @@
 from a table of directions, walked and counted on the device — how many are occluded and the sum of the directions that are not.  As with
 _lib.py there is no fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from . import _abi, _hiprt, _lib
-from ._lib import HiprzError
+from . import _abi, _hiprt, _satellite
 from .query import ray_dtype
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("HIPRZ_BAKE_LIB") or os.path.join(_HERE, "csrc", "libhiprz_bake.so")
+LIB_PATH = _satellite.lib_path("HIPRZ_BAKE_LIB", "libhiprz_bake.so")
 INVALID = 0x80000000                              # HIPRZ_BAKE_INVALID
-_lib_bake = None
 
 point_dtype = np.dtype([("position", "<f4", 3), ("near", "<f4"), ("normal", "<f4", 3), ("far", "<f4")])      # hiprz_bake_point
 texel_dtype = np.dtype([("bent", "<f4", 3), ("occluded", "<u4")])                                            # hiprz_bake_texel
@@ -35,19 +31,7 @@ ENTRY_POINTS = {
 
 
 def load():
-    global _lib_bake
-    if _lib_bake is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(
-                f"{LIB_PATH} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). "
-                "rayzath_amd has no CPU fallback.")
-        _lib.load()  # libhiprz.so first: the bake library reads contexts through its hiprz_device_view
-        lib = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in ENTRY_POINTS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib_bake = lib
-    return _lib_bake
+    return _satellite.load(LIB_PATH, ENTRY_POINTS)
 
 
 def points(position, normal, near=1.0e-3, far=3.0e38):
@@ -71,21 +55,14 @@ def set_of(i, seed, S):
     return int(load().hiprz_bake_set_of(i, seed, S))
 
 
-class Bake:
+class Bake(_satellite.Handle):
     """Owns one hiprz_bake bound to the hiprz_ctx `ctx_ptr`; close it before the context."""
+    _bake = property(lambda self: self._handle)
 
     def __init__(self, ctx_ptr):
-        self.lib = load()
-        self._bake = C.c_void_p()
         self.K = self.S = 0
         self.table = None         # the (K, S) of a cosine table set through set_directions, None for a caller's array or none
-        rc = self.lib.hiprz_bake_create(C.byref(self._bake), ctx_ptr)
-        if rc != _abi.OK:
-            raise HiprzError(rc, (self.lib.hiprz_bake_last_error(None) or b"").decode())
-
-    def _check(self, rc):
-        if rc != _abi.OK:
-            raise HiprzError(rc, (self.lib.hiprz_bake_last_error(self._bake) or b"").decode())
+        super().__init__(load(), "bake", ctx_ptr)
 
     def set_directions(self, directions):
         """directions: an (S, K, 4) float32 array of unit vectors in the local frame (z along the normal), or a (K, S) pair for the cosine table"""
@@ -138,14 +115,3 @@ class Bake:
             return d_rays.download(points.shape + (self.K,), ray_dtype)
         finally:
             d_points.free(), d_rays.free()
-
-    def close(self):
-        if self._bake:
-            self.lib.hiprz_bake_destroy(self._bake)
-            self._bake = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

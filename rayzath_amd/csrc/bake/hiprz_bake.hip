@@ -5,13 +5,13 @@
 // hiprz_device_view on every call.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "hiprz_bake.h"
 #include "hiprz_bake_host.hpp"
 #include "query/hiprz_query_device.hpp"
+#include "query/hiprz_session.hpp"  // the handle, its errors, the view, the staging and its round trip
 
 // threads per workgroup: one wave — the ballot and the butterfly span exactly the workgroup
 #define RZ_BAKE_WG 64
@@ -115,43 +115,14 @@ using namespace hiprz;
 
 static_assert(sizeof(hiprz_bake_point) == 32 && sizeof(hiprz_bake_texel) == 16 && sizeof(hiprz_ray) == 32, "two 16-byte loads per point, one 16-byte store per texel");
 
-struct hiprz_bake {
-    hiprz_ctx* ctx = nullptr;
-    int device = -1;            // the context's head device, known from the first view on (hiprz_device_view makes it current)
-    std::vector<float> table;   // the directions as set, S*K float4 with w = 0; K == 0: none yet
+struct hiprz_bake : Session {
+    std::vector<float> table;  // the directions as set, S*K float4 with w = 0; K == 0: none yet
     uint32_t K = 0, S = 0;
-    float4* dirs = nullptr;     // the device copy, made by the first call after set_directions (`stale`)
+    float4* dirs = nullptr;    // the device copy, made by the first call after set_directions (`stale`)
     bool stale = false;
-    void* pinned_points = nullptr;  // host-pointer call: pinned staging and its device twin, `capacity` points each
-    void* pinned_out = nullptr;
-    void* dev_points = nullptr;
-    void* dev_out = nullptr;
-    size_t capacity = 0;
-    std::string error;
 };
 
 namespace {
-thread_local std::string g_error;  // of calls without a handle
-
-int fail(hiprz_bake* b, int code, const std::string& message) {
-    (b ? b->error : g_error) = message;
-    return code;
-}
-int fail_hip(hiprz_bake* b, const char* what, hipError_t e) { return fail(b, HIPRZ_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-
-// the context's scene view, fetched on every call; the size is the guard against a libhiprz.so built from other headers
-int view(hiprz_bake* b, const char* what, DScene& s) {
-    const int rc = hiprz_device_view(b->ctx, &s, sizeof s, nullptr, 0u);
-    if (rc != HIPRZ_OK) {
-        const char* why = hiprz_last_error(b->ctx);
-        return fail(b, rc, std::string(what) + ": " + (why && *why ? why : "the context gave no device view"));
-    }
-    if (const hipError_t e = hipGetDevice(&b->device); e != hipSuccess) return fail_hip(b, what, e);
-    return HIPRZ_OK;
-}
-
-hipStream_t stream_of(hiprz_bake* b, void* stream) { return static_cast<hipStream_t>(stream ? stream : hiprz_stream(b->ctx)); }
-
 // what every call refuses before anything is launched or copied; *empty: nothing to do (n == 0 is HIPRZ_OK without a view or a launch)
 int refuse(hiprz_bake* b, bool any_null, size_t n, const char* what, bool* empty) {
     *empty = false;
@@ -176,30 +147,6 @@ int place_table(hiprz_bake* b, hipStream_t stream, const char* what) {
     return HIPRZ_OK;
 }
 
-void release_staging(hiprz_bake* b) {
-    if (b->dev_points) (void)hipFree(b->dev_points);
-    if (b->dev_out) (void)hipFree(b->dev_out);
-    if (b->pinned_points) (void)hipHostFree(b->pinned_points);
-    if (b->pinned_out) (void)hipHostFree(b->pinned_out);
-    b->dev_points = b->dev_out = b->pinned_points = b->pinned_out = nullptr, b->capacity = 0;
-}
-
-int grow_staging(hiprz_bake* b, size_t n, const char* what) {
-    if (n <= b->capacity) return HIPRZ_OK;
-    const size_t cap = bake_capacity(b->capacity, n);
-    release_staging(b);
-    hipError_t e = hipMalloc(&b->dev_points, cap * sizeof(hiprz_bake_point));
-    if (e == hipSuccess) e = hipMalloc(&b->dev_out, cap * sizeof(hiprz_bake_texel));
-    if (e == hipSuccess) e = hipHostMalloc(&b->pinned_points, cap * sizeof(hiprz_bake_point), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&b->pinned_out, cap * sizeof(hiprz_bake_texel), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        release_staging(b);
-        return fail_hip(b, what, e);
-    }
-    b->capacity = cap;
-    return HIPRZ_OK;
-}
-
 // the bake of n device points on the view the call has fetched
 int launch_occlusion(hiprz_bake* b, const DScene& s, const hiprz_bake_point* points, size_t n, uint32_t seed, hiprz_bake_texel* out, hipStream_t stream,
                      const char* what) {
@@ -215,31 +162,13 @@ int launch_occlusion(hiprz_bake* b, const DScene& s, const hiprz_bake_point* poi
 
 extern "C" {
 
-int hiprz_bake_create(hiprz_bake** out, hiprz_ctx* ctx) {
-    if (!out) return fail(nullptr, HIPRZ_ERR_INVALID, "bake_create: null output");
-    *out = nullptr;
-    int n = 0;
-    if (const hipError_t e = hipGetDeviceCount(&n); e != hipSuccess || n <= 0)
-        return fail(nullptr, HIPRZ_ERR_DEVICE, std::string("no HIP device: ") + hipGetErrorString(e));
-    if (!ctx) return fail(nullptr, HIPRZ_ERR_INVALID, "bake_create: null context");
-    hiprz_bake* b = new hiprz_bake;
-    b->ctx = ctx;
-    *out = b;
-    return HIPRZ_OK;
-}
+int hiprz_bake_create(hiprz_bake** out, hiprz_ctx* ctx) { return create(out, ctx, "bake_create"); }
 
 int hiprz_bake_destroy(hiprz_bake* b) {
-    if (!b) return HIPRZ_ERR_INVALID;
-    if (b->capacity || b->dirs) {
-        (void)hipSetDevice(b->device);
-        release_staging(b);
-        if (b->dirs) (void)hipFree(b->dirs);
-    }
-    delete b;
-    return HIPRZ_OK;
+    return destroy(b, b && b->dirs, [b] { if (b->dirs) (void)hipFree(b->dirs); });
 }
 
-const char* hiprz_bake_last_error(const hiprz_bake* b) { return b ? b->error.c_str() : g_error.c_str(); }
+const char* hiprz_bake_last_error(const hiprz_bake* b) { return last_error(b); }
 
 int hiprz_bake_set_directions(hiprz_bake* b, const float* xyz0_host, uint32_t K, uint32_t S) {
     if (!b) return fail(nullptr, HIPRZ_ERR_INVALID, "bake_set_directions: null bake");
@@ -280,19 +209,10 @@ int hiprz_bake_occlusion_host(hiprz_bake* b, const hiprz_bake_point* points, siz
     if (const int rc = refuse(b, !points || !out, n, what, &empty); rc != HIPRZ_OK || empty) return rc;
     DScene s;
     if (const int rc = view(b, what, s); rc != HIPRZ_OK) return rc;  // refuses first, and makes the head device current for the staging
-    if (const int rc = grow_staging(b, n, what); rc != HIPRZ_OK) return rc;
-    hipStream_t st = stream_of(b, nullptr);
-    std::memcpy(b->pinned_points, points, n * sizeof(hiprz_bake_point));
-    if (const hipError_t e = hipMemcpyAsync(b->dev_points, b->pinned_points, n * sizeof(hiprz_bake_point), hipMemcpyHostToDevice, st); e != hipSuccess)
-        return fail_hip(b, what, e);
-    if (const int rc = launch_occlusion(b, s, static_cast<const hiprz_bake_point*>(b->dev_points), n, seed, static_cast<hiprz_bake_texel*>(b->dev_out), st, what);
-        rc != HIPRZ_OK)
-        return rc;
-    if (const hipError_t e = hipMemcpyAsync(b->pinned_out, b->dev_out, n * sizeof(hiprz_bake_texel), hipMemcpyDeviceToHost, st); e != hipSuccess)
-        return fail_hip(b, what, e);
-    if (const hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail_hip(b, what, e);
-    std::memcpy(out, b->pinned_out, n * sizeof(hiprz_bake_texel));
-    return HIPRZ_OK;
+    if (const int rc = grow_staging(b, what, n, sizeof(hiprz_bake_point), sizeof(hiprz_bake_texel), bake_capacity); rc != HIPRZ_OK) return rc;
+    return round_trip(b, what, points, n, sizeof(hiprz_bake_point), out, sizeof(hiprz_bake_texel), [&](void* dev_points, void* dev_out, hipStream_t st) {
+        return launch_occlusion(b, s, static_cast<const hiprz_bake_point*>(dev_points), n, seed, static_cast<hiprz_bake_texel*>(dev_out), st, what);
+    });
 }
 
 }  // extern "C"

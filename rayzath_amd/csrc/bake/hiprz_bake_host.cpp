@@ -35,11 +35,7 @@ const char* bake_refusal(bool any_null, size_t n, uint32_t K, int* code) {
     return nullptr;
 }
 
-size_t bake_capacity(size_t have, size_t need) {
-    if (need <= have) return have;
-    const size_t cap = query_staging_capacity(have, need);
-    return cap > kBakeMaxPoints ? kBakeMaxPoints : cap;
-}
+size_t bake_capacity(size_t have, size_t need) { return staging_capacity(have, need, kBakeMaxPoints); }
 
 }  // namespace hiprz
 

@@ -4,12 +4,12 @@
 // (query/hiprz_query_device.hpp, no __global__), so the bytes are its bytes.  The context is read through hiprz_device_view on every call.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <string>
 
 #include "hiprz_order.h"
 #include "hiprz_order_host.hpp"
 #include "query/hiprz_query_device.hpp"
+#include "query/hiprz_session.hpp"  // the handle, its errors, the view, the staging and its round trip
 
 // threads per workgroup: one wave, as RZ_QUERY_WG measured for the same walks (DESIGN.md "Ray queries")
 #ifndef RZ_ORDER_WG
@@ -62,42 +62,13 @@ using namespace hiprz;
 
 static_assert(sizeof(hiprz_ray) == 32 && sizeof(hiprz_hit) == 48, "two 16-byte loads per ray, three 16-byte stores per hit");
 
-struct hiprz_order {
-    hiprz_ctx* ctx = nullptr;
-    int device = -1;             // the context's head device, known from the first view on (hiprz_device_view makes it current)
-    uint32_t* keys = nullptr;    // fused calls: the keys the sort consumes and the order it leaves, `work_capacity` words each
+struct hiprz_order : Session {
+    uint32_t* keys = nullptr;  // fused calls: the keys the sort consumes and the order it leaves, `work_capacity` words each
     uint32_t* perm = nullptr;
     size_t work_capacity = 0;
-    void* pinned_rays = nullptr;  // host-pointer calls: pinned staging and its device twin, `capacity` rays each
-    void* pinned_out = nullptr;
-    void* dev_rays = nullptr;
-    void* dev_out = nullptr;
-    size_t capacity = 0;
-    std::string error;
 };
 
 namespace {
-thread_local std::string g_error;  // of calls without a handle
-
-int fail(hiprz_order* o, int code, const std::string& message) {
-    (o ? o->error : g_error) = message;
-    return code;
-}
-int fail_hip(hiprz_order* o, const char* what, hipError_t e) { return fail(o, HIPRZ_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-
-// the context's scene view, fetched on every call; the size is the guard against a libhiprz.so built from other headers
-int view(hiprz_order* o, const char* what, DScene& s) {
-    const int rc = hiprz_device_view(o->ctx, &s, sizeof s, nullptr, 0u);
-    if (rc != HIPRZ_OK) {
-        const char* why = hiprz_last_error(o->ctx);
-        return fail(o, rc, std::string(what) + ": " + (why && *why ? why : "the context gave no device view"));
-    }
-    if (const hipError_t e = hipGetDevice(&o->device); e != hipSuccess) return fail_hip(o, what, e);
-    return HIPRZ_OK;
-}
-
-hipStream_t stream_of(hiprz_order* o, void* stream) { return static_cast<hipStream_t>(stream ? stream : hiprz_stream(o->ctx)); }
-
 uint32_t grid_of(size_t n) { return uint32_t((n + RZ_ORDER_WG - 1u) / RZ_ORDER_WG); }
 
 // what every call refuses before anything is launched or copied; *empty: nothing to do (n == 0 is HIPRZ_OK without a view or a launch)
@@ -126,31 +97,6 @@ int grow_work(hiprz_order* o, size_t n, const char* what) {
         return fail_hip(o, what, e);
     }
     o->work_capacity = cap;
-    return HIPRZ_OK;
-}
-
-void release_staging(hiprz_order* o) {
-    if (o->dev_rays) (void)hipFree(o->dev_rays);
-    if (o->dev_out) (void)hipFree(o->dev_out);
-    if (o->pinned_rays) (void)hipHostFree(o->pinned_rays);
-    if (o->pinned_out) (void)hipHostFree(o->pinned_out);
-    o->dev_rays = o->dev_out = o->pinned_rays = o->pinned_out = nullptr, o->capacity = 0;
-}
-
-// the output side is sized for hits: occlusion words fit in it
-int grow_staging(hiprz_order* o, size_t n, const char* what) {
-    if (n <= o->capacity) return HIPRZ_OK;
-    const size_t cap = order_capacity(o->capacity, n);
-    release_staging(o);
-    hipError_t e = hipMalloc(&o->dev_rays, cap * sizeof(hiprz_ray));
-    if (e == hipSuccess) e = hipMalloc(&o->dev_out, cap * sizeof(hiprz_hit));
-    if (e == hipSuccess) e = hipHostMalloc(&o->pinned_rays, cap * sizeof(hiprz_ray), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&o->pinned_out, cap * sizeof(hiprz_hit), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        release_staging(o);
-        return fail_hip(o, what, e);
-    }
-    o->capacity = cap;
     return HIPRZ_OK;
 }
 
@@ -203,46 +149,23 @@ int host_call(hiprz_order* o, const hiprz_ray* rays, size_t n, uint32_t flags, O
     if (const int rc = refuse(o, !rays || !out, n, flags, what, &empty); rc != HIPRZ_OK || empty) return rc;
     DScene s;
     if (const int rc = view(o, what, s); rc != HIPRZ_OK) return rc;  // refuses first, and makes the head device current for the staging
-    if (const int rc = grow_staging(o, n, what); rc != HIPRZ_OK) return rc;
-    hipStream_t st = stream_of(o, nullptr);
-    std::memcpy(o->pinned_rays, rays, n * sizeof(hiprz_ray));
-    if (const hipError_t e = hipMemcpyAsync(o->dev_rays, o->pinned_rays, n * sizeof(hiprz_ray), hipMemcpyHostToDevice, st); e != hipSuccess)
-        return fail_hip(o, what, e);
-    if (const int rc = fused(o, s, static_cast<const hiprz_ray*>(o->dev_rays), n, flags, static_cast<Out*>(o->dev_out), st, what); rc != HIPRZ_OK) return rc;
-    if (const hipError_t e = hipMemcpyAsync(o->pinned_out, o->dev_out, n * sizeof(Out), hipMemcpyDeviceToHost, st); e != hipSuccess) return fail_hip(o, what, e);
-    if (const hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail_hip(o, what, e);
-    std::memcpy(out, o->pinned_out, n * sizeof(Out));
-    return HIPRZ_OK;
+    // the output side is sized for hits: occlusion words fit in it
+    if (const int rc = grow_staging(o, what, n, sizeof(hiprz_ray), sizeof(hiprz_hit), order_capacity); rc != HIPRZ_OK) return rc;
+    return round_trip(o, what, rays, n, sizeof(hiprz_ray), out, sizeof(Out), [&](void* dev_rays, void* dev_out, hipStream_t st) {
+        return fused(o, s, static_cast<const hiprz_ray*>(dev_rays), n, flags, static_cast<Out*>(dev_out), st, what);
+    });
 }
 }  // namespace
 
 extern "C" {
 
-int hiprz_order_create(hiprz_order** out, hiprz_ctx* ctx) {
-    if (!out) return fail(nullptr, HIPRZ_ERR_INVALID, "order_create: null output");
-    *out = nullptr;
-    int n = 0;
-    if (const hipError_t e = hipGetDeviceCount(&n); e != hipSuccess || n <= 0)
-        return fail(nullptr, HIPRZ_ERR_DEVICE, std::string("no HIP device: ") + hipGetErrorString(e));
-    if (!ctx) return fail(nullptr, HIPRZ_ERR_INVALID, "order_create: null context");
-    hiprz_order* o = new hiprz_order;
-    o->ctx = ctx;
-    *out = o;
-    return HIPRZ_OK;
-}
+int hiprz_order_create(hiprz_order** out, hiprz_ctx* ctx) { return create(out, ctx, "order_create"); }
 
 int hiprz_order_destroy(hiprz_order* o) {
-    if (!o) return HIPRZ_ERR_INVALID;
-    if (o->capacity || o->work_capacity) {
-        (void)hipSetDevice(o->device);
-        release_staging(o);
-        release_work(o);
-    }
-    delete o;
-    return HIPRZ_OK;
+    return destroy(o, o && o->work_capacity, [o] { release_work(o); });
 }
 
-const char* hiprz_order_last_error(const hiprz_order* o) { return o ? o->error.c_str() : g_error.c_str(); }
+const char* hiprz_order_last_error(const hiprz_order* o) { return last_error(o); }
 
 int hiprz_order_permutation(hiprz_order* o, const hiprz_ray* rays_device, size_t n, uint32_t flags, uint32_t* keys_out_device, uint32_t* perm_out_device,
                             void* stream) {

@@ -4,11 +4,11 @@
 // kernel of that library is duplicated here; the context is read through hiprz_device_view on every call.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <string>
 
 #include "hiprz_query_device.hpp"  // hiprz_device.hpp, hiprz_query.h, and the ray rule and records shared with libhiprz_order.so
 #include "hiprz_query_staging.hpp"
+#include "hiprz_session.hpp"  // the handle, its errors, the view, the staging and its round trip
 
 // threads per workgroup.  One wave: ray costs are heavy-tailed, and a single-wave workgroup gives its slot back as soon as ITS slowest ray
 // is done instead of waiting for the slowest of four waves (DESIGN.md "Ray queries" has both measurements).
@@ -53,50 +53,16 @@ using namespace hiprz;
 
 static_assert(sizeof(hiprz_ray) == 32 && sizeof(hiprz_hit) == 48, "two 16-byte loads per ray, three 16-byte stores per hit");
 
-struct hiprz_query {
-    hiprz_ctx* ctx = nullptr;
-    int device = -1;            // the context's head device, known from the first view on (hiprz_device_view makes it current)
-    void* pinned_rays = nullptr;  // host-pointer calls: pinned staging and its device twin, `capacity` rays each
-    void* pinned_out = nullptr;
-    void* dev_rays = nullptr;
-    void* dev_out = nullptr;
-    size_t capacity = 0;
-    std::string error;
-};
+struct hiprz_query : Session {};  // the staging holds rays and, on the out side, hits: occlusion words fit in it
 
 namespace {
-thread_local std::string g_error;  // of calls without a query
-
-constexpr size_t kMaxRays = 0x7FFFFFFFull;
-
-int fail(hiprz_query* q, int code, const std::string& message) {
-    (q ? q->error : g_error) = message;
-    return code;
-}
-int fail_hip(hiprz_query* q, const char* what, hipError_t e) { return fail(q, HIPRZ_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-
-// the context's device views, fetched on every call; the sizes are the guard against a libhiprz.so built from other headers
-int view(hiprz_query* q, const char* what, DScene& s, DCamera* cam) {
-    const int rc = hiprz_device_view(q->ctx, &s, sizeof s, cam, cam ? sizeof *cam : 0u);
-    if (rc != HIPRZ_OK) {
-        const char* why = hiprz_last_error(q->ctx);
-        return fail(q, rc, std::string(what) + ": " + (why && *why ? why : "the context gave no device view"));
-    }
-    if (const hipError_t e = hipGetDevice(&q->device); e != hipSuccess) return fail_hip(q, what, e);
-    return HIPRZ_OK;
-}
-
-hipStream_t stream_of(hiprz_query* q, void* stream) { return static_cast<hipStream_t>(stream ? stream : hiprz_stream(q->ctx)); }
-
 uint32_t grid_of(size_t n) { return uint32_t((n + RZ_QUERY_WG - 1u) / RZ_QUERY_WG); }
 
 // what every call refuses before anything is launched or copied; *empty: nothing to do (n == 0 is HIPRZ_OK without a view or a launch)
 int refuse(hiprz_query* q, const void* rays, size_t n, uint32_t flags, const void* out, const char* what, bool* empty) {
     *empty = false;
     if (!q) return fail(nullptr, HIPRZ_ERR_INVALID, std::string(what) + ": null query");
-    if (!rays || !out) return fail(q, HIPRZ_ERR_INVALID, std::string(what) + ": null pointer");
-    if (flags & ~HIPRZ_QUERY_NORMALIZE) return fail(q, HIPRZ_ERR_INVALID, std::string(what) + ": unknown flag");
-    if (n > kMaxRays) return fail(q, HIPRZ_ERR_INVALID, std::string(what) + ": more than 2^31 - 1 rays");
+    if (const char* why = query_refusal(!rays || !out, n, flags)) return fail(q, HIPRZ_ERR_INVALID, std::string(what) + ": " + why);
     *empty = n == 0u;
     return HIPRZ_OK;
 }
@@ -118,33 +84,8 @@ int enqueue(hiprz_query* q, const hiprz_ray* rays, size_t n, uint32_t flags, Out
     bool empty;
     if (const int rc = refuse(q, rays, n, flags, out, what, &empty); rc != HIPRZ_OK || empty) return rc;
     DScene s;
-    if (const int rc = view(q, what, s, nullptr); rc != HIPRZ_OK) return rc;
+    if (const int rc = view(q, what, s); rc != HIPRZ_OK) return rc;
     return launch(q, s, rays, n, flags, out, stream_of(q, stream), what);
-}
-
-void release_staging(hiprz_query* q) {
-    if (q->dev_rays) (void)hipFree(q->dev_rays);  // (hipFree waits for whatever still uses the buffer)
-    if (q->dev_out) (void)hipFree(q->dev_out);
-    if (q->pinned_rays) (void)hipHostFree(q->pinned_rays);
-    if (q->pinned_out) (void)hipHostFree(q->pinned_out);
-    q->dev_rays = q->dev_out = q->pinned_rays = q->pinned_out = nullptr, q->capacity = 0;
-}
-
-// the output side is sized for hits: occlusion words fit in it
-int grow_staging(hiprz_query* q, size_t n, const char* what) {
-    if (n <= q->capacity) return HIPRZ_OK;
-    const size_t cap = query_staging_capacity(q->capacity, n);
-    release_staging(q);
-    hipError_t e = hipMalloc(&q->dev_rays, cap * sizeof(hiprz_ray));
-    if (e == hipSuccess) e = hipMalloc(&q->dev_out, cap * sizeof(hiprz_hit));
-    if (e == hipSuccess) e = hipHostMalloc(&q->pinned_rays, cap * sizeof(hiprz_ray), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&q->pinned_out, cap * sizeof(hiprz_hit), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        release_staging(q);
-        return fail_hip(q, what, e);
-    }
-    q->capacity = cap;
-    return HIPRZ_OK;
 }
 
 template <typename Out>
@@ -152,46 +93,21 @@ int host_call(hiprz_query* q, const hiprz_ray* rays, size_t n, uint32_t flags, O
     bool empty;
     if (const int rc = refuse(q, rays, n, flags, out, what, &empty); rc != HIPRZ_OK || empty) return rc;
     DScene s;
-    if (const int rc = view(q, what, s, nullptr); rc != HIPRZ_OK) return rc;  // refuses first, and makes the head device current for the staging
-    if (const int rc = grow_staging(q, n, what); rc != HIPRZ_OK) return rc;
-    hipStream_t st = stream_of(q, nullptr);
-    std::memcpy(q->pinned_rays, rays, n * sizeof(hiprz_ray));
-    if (const hipError_t e = hipMemcpyAsync(q->dev_rays, q->pinned_rays, n * sizeof(hiprz_ray), hipMemcpyHostToDevice, st); e != hipSuccess)
-        return fail_hip(q, what, e);
-    if (const int rc = launch(q, s, static_cast<const hiprz_ray*>(q->dev_rays), n, flags, static_cast<Out*>(q->dev_out), st, what); rc != HIPRZ_OK) return rc;
-    if (const hipError_t e = hipMemcpyAsync(q->pinned_out, q->dev_out, n * sizeof(Out), hipMemcpyDeviceToHost, st); e != hipSuccess) return fail_hip(q, what, e);
-    if (const hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return fail_hip(q, what, e);
-    std::memcpy(out, q->pinned_out, n * sizeof(Out));
-    return HIPRZ_OK;
+    if (const int rc = view(q, what, s); rc != HIPRZ_OK) return rc;  // refuses first, and makes the head device current for the staging
+    if (const int rc = grow_staging(q, what, n, sizeof(hiprz_ray), sizeof(hiprz_hit), query_staging_capacity); rc != HIPRZ_OK) return rc;
+    return round_trip(q, what, rays, n, sizeof(hiprz_ray), out, sizeof(Out), [&](void* dev_rays, void* dev_out, hipStream_t st) {
+        return launch(q, s, static_cast<const hiprz_ray*>(dev_rays), n, flags, static_cast<Out*>(dev_out), st, what);
+    });
 }
 }  // namespace
 
 extern "C" {
 
-int hiprz_query_create(hiprz_query** out, hiprz_ctx* ctx) {
-    if (!out) return fail(nullptr, HIPRZ_ERR_INVALID, "query_create: null output");
-    *out = nullptr;
-    int n = 0;
-    if (const hipError_t e = hipGetDeviceCount(&n); e != hipSuccess || n <= 0)
-        return fail(nullptr, HIPRZ_ERR_DEVICE, std::string("no HIP device: ") + hipGetErrorString(e));
-    if (!ctx) return fail(nullptr, HIPRZ_ERR_INVALID, "query_create: null context");
-    hiprz_query* q = new hiprz_query;
-    q->ctx = ctx;
-    *out = q;
-    return HIPRZ_OK;
-}
+int hiprz_query_create(hiprz_query** out, hiprz_ctx* ctx) { return create(out, ctx, "query_create"); }
 
-int hiprz_query_destroy(hiprz_query* q) {
-    if (!q) return HIPRZ_ERR_INVALID;
-    if (q->capacity) {
-        (void)hipSetDevice(q->device);
-        release_staging(q);
-    }
-    delete q;
-    return HIPRZ_OK;
-}
+int hiprz_query_destroy(hiprz_query* q) { return destroy(q); }
 
-const char* hiprz_query_last_error(const hiprz_query* q) { return q ? q->error.c_str() : g_error.c_str(); }
+const char* hiprz_query_last_error(const hiprz_query* q) { return last_error(q); }
 
 int hiprz_query_closest(hiprz_query* q, const hiprz_ray* rays_device, size_t n, uint32_t flags, hiprz_hit* hits_out_device, void* stream) {
     return enqueue(q, rays_device, n, flags, hits_out_device, stream, "query_closest");
@@ -217,7 +133,7 @@ int hiprz_query_pixel_rays(hiprz_query* q, hiprz_ray* rays_out_device, void* str
     if (const int rc = view(q, "query_pixel_rays", s, &cam); rc != HIPRZ_OK) return rc;
     const size_t n = size_t(cam.width) * cam.height;
     if (n == 0u) return HIPRZ_OK;
-    if (n > kMaxRays) return fail(q, HIPRZ_ERR_INVALID, "query_pixel_rays: more than 2^31 - 1 pixels");
+    if (n > kQueryMaxRays) return fail(q, HIPRZ_ERR_INVALID, "query_pixel_rays: more than 2^31 - 1 pixels");
     hipLaunchKernelGGL(rz_query_pixel_rays_kernel, dim3(grid_of(n)), dim3(RZ_QUERY_WG), 0, stream_of(q, stream), cam, reinterpret_cast<float4*>(rays_out_device));
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail_hip(q, "query_pixel_rays", e);
     return HIPRZ_OK;

@@ -2,17 +2,13 @@
 for incoherent batches, walked in the renderer's sorted ray order; the result bytes are query.py's.  As with _lib.py there is no fallback:
 a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from . import _abi, _hiprt, _lib
-from ._lib import HiprzError
-from .query import NORMALIZE, hit_dtype, ray_dtype
+from . import _hiprt, _satellite
+from .query import NORMALIZE, hit_dtype, ray_dtype, ray_records
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("HIPRZ_ORDER_LIB") or os.path.join(_HERE, "csrc", "libhiprz_order.so")
-_lib_order = None
+LIB_PATH = _satellite.lib_path("HIPRZ_ORDER_LIB", "libhiprz_order.so")
 
 P, U32, SZ = C.c_void_p, C.c_uint32, C.c_size_t
 ENTRY_POINTS = {
@@ -30,41 +26,16 @@ ENTRY_POINTS = {
 
 
 def load():
-    global _lib_order
-    if _lib_order is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(
-                f"{LIB_PATH} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). "
-                "rayzath_amd has no CPU fallback.")
-        _lib.load()  # libhiprz.so first: the order library reads contexts through hiprz_device_view and sorts through hiprz_sort_u32_device
-        lib = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in ENTRY_POINTS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib_order = lib
-    return _lib_order
+    return _satellite.load(LIB_PATH, ENTRY_POINTS)
 
 
-class Order:
+class Order(_satellite.Handle):
     """Owns one hiprz_order bound to the hiprz_ctx `ctx_ptr`; close it before the context."""
+    _order = property(lambda self: self._handle)
+    _rays = staticmethod(ray_records)
 
     def __init__(self, ctx_ptr):
-        self.lib = load()
-        self._order = C.c_void_p()
-        rc = self.lib.hiprz_order_create(C.byref(self._order), ctx_ptr)
-        if rc != _abi.OK:
-            raise HiprzError(rc, (self.lib.hiprz_order_last_error(None) or b"").decode())
-
-    def _check(self, rc):
-        if rc != _abi.OK:
-            raise HiprzError(rc, (self.lib.hiprz_order_last_error(self._order) or b"").decode())
-
-    @staticmethod
-    def _rays(rays):
-        rays = np.ascontiguousarray(rays)
-        if rays.dtype != ray_dtype:
-            raise TypeError("rays must be an array of rayzath_amd.query.ray_dtype")
-        return rays
+        super().__init__(load(), "order", ctx_ptr)
 
     def closest(self, rays, normalize=False):
         """query.Query.closest's hits of host rays, walked in sorted order; waits for the context's stream"""
@@ -114,14 +85,3 @@ class Order:
             self._check(self.lib.hiprz_order_occluded(self._order, rays_ptr, n, flags, out_ptr, stream))
         else:
             self._check(self.lib.hiprz_order_occluded_by(self._order, rays_ptr, perm_ptr, n, flags, out_ptr, stream))
-
-    def close(self):
-        if self._order:
-            self.lib.hiprz_order_destroy(self._order)
-            self._order = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

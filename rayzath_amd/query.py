@@ -1,18 +1,14 @@
 """Loader and ctypes mirror of the ray queries (include/hiprz_query.h, rayzath_amd/csrc/libhiprz_query.so): closest hit and occlusion for
 caller-supplied rays in the world a context holds.  As with _lib.py there is no fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from . import _abi, _lib
-from ._lib import HiprzError
+from . import _satellite
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("HIPRZ_QUERY_LIB") or os.path.join(_HERE, "csrc", "libhiprz_query.so")
+LIB_PATH = _satellite.lib_path("HIPRZ_QUERY_LIB", "libhiprz_query.so")
 NORMALIZE = 1                                     # HIPRZ_QUERY_NORMALIZE
 HIT_FOUND, HIT_EXTERNAL, HIT_INVALID = 1, 2, 4    # hiprz_hit::flags
-_lib_query = None
 
 ray_dtype = np.dtype([("origin", "<f4", 3), ("near", "<f4"), ("direction", "<f4", 3), ("far", "<f4")])      # hiprz_ray
 hit_dtype = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("flags", "<u4"), ("instance", "<i4"), ("material_slot", "<i4"),
@@ -34,19 +30,7 @@ ENTRY_POINTS = {
 
 
 def load():
-    global _lib_query
-    if _lib_query is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(
-                f"{LIB_PATH} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). "
-                "rayzath_amd has no CPU fallback.")
-        _lib.load()  # libhiprz.so first: the query library reads contexts through its hiprz_device_view
-        lib = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in ENTRY_POINTS.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _lib_query = lib
-    return _lib_query
+    return _satellite.load(LIB_PATH, ENTRY_POINTS)
 
 
 def rays(origin, direction, near=0.0, far=3.0e38):
@@ -57,26 +41,21 @@ def rays(origin, direction, near=0.0, far=3.0e38):
     return out
 
 
-class Query:
+def ray_records(rays):
+    """`rays` as a contiguous array of ray_dtype, for a call that takes its address"""
+    rays = np.ascontiguousarray(rays)
+    if rays.dtype != ray_dtype:
+        raise TypeError("rays must be an array of rayzath_amd.query.ray_dtype")
+    return rays
+
+
+class Query(_satellite.Handle):
     """Owns one hiprz_query bound to the hiprz_ctx `ctx_ptr`; close it before the context."""
+    _query = property(lambda self: self._handle)
+    _rays = staticmethod(ray_records)
 
     def __init__(self, ctx_ptr):
-        self.lib = load()
-        self._query = C.c_void_p()
-        rc = self.lib.hiprz_query_create(C.byref(self._query), ctx_ptr)
-        if rc != _abi.OK:
-            raise HiprzError(rc, (self.lib.hiprz_query_last_error(None) or b"").decode())
-
-    def _check(self, rc):
-        if rc != _abi.OK:
-            raise HiprzError(rc, (self.lib.hiprz_query_last_error(self._query) or b"").decode())
-
-    @staticmethod
-    def _rays(rays):
-        rays = np.ascontiguousarray(rays)
-        if rays.dtype != ray_dtype:
-            raise TypeError("rays must be an array of rayzath_amd.query.ray_dtype")
-        return rays
+        super().__init__(load(), "query", ctx_ptr)
 
     def closest(self, rays, normalize=False):
         """hits (hit_dtype, the shape of `rays`) of host rays; waits for the context's stream"""
@@ -102,14 +81,3 @@ class Query:
     def pixel_rays_device(self, rays_ptr, stream=None):
         """enqueue only: the selected camera's W*H pixel-centre rays, row-major, to the device address rays_ptr"""
         self._check(self.lib.hiprz_query_pixel_rays(self._query, rays_ptr, stream))
-
-    def close(self):
-        if self._query:
-            self.lib.hiprz_query_destroy(self._query)
-            self._query = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,6 +1,7 @@
 // query_host_main.cpp — the pure-host units of the ray queries (rayzath_amd/csrc/query/hiprz_query_staging.hpp, hiprz_query_host.cpp) as a
 // process of its own, for tests/test_query_abi.py to build under sanitizers: reads "have need" pairs from stdin, prints
-// query_staging_capacity of each (a staging of that capacity is allocated and touched where `need` ends), then the layout words.
+// query_staging_capacity of each (a staging of that capacity is allocated and touched where `need` ends), then the query's refusals of the
+// calls tests/order_host_main.cpp lists (under the query's limit of 2^31 - 1 rays), then the layout words.
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -20,6 +21,16 @@ int main() {
             if (need) std::memset(&rays[need - 1], 0, sizeof(hiprz_ray)), std::memset(&hits[need - 1], 0, sizeof(hiprz_hit));
         }
         ++pairs;
+    }
+    const struct {
+        bool any_null;
+        size_t n;
+        uint32_t flags;
+    } calls[] = {{false, 0, 0},           {false, 1, HIPRZ_QUERY_NORMALIZE}, {true, 1, 0},  {false, 1, 2},       {false, 1, 3},
+                 {false, size_t(1) << 30, 0}, {false, (size_t(1) << 30) + 1, 0}, {true, 0, 2}, {false, ~size_t(0), 1}};
+    for (const auto& c : calls) {
+        const char* why = hiprz::query_refusal(c.any_null, c.n, c.flags);
+        std::printf("refusal: %s\n", why ? why : "none");
     }
     uint32_t layout[7];
     hiprz_query_layout(layout);

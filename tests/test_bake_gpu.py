@@ -17,7 +17,8 @@ All eight were kept; case 3 asserts the condition again on the points it samples
                  verdicts bit for bit: every point of the scene, both far_, K in 16, 64, 128.
   3 oracle       at most 64 points per scene and far_, K = 16: the oracle's "found" on every emitted ray == the verdict the count is made of.
   4 shapes       n in 1, 3, 4, 5, 63, 64, 65, 257 at K in 16, 32, 64, 128 through device pointers with guard words behind the texels and
-                 the rays; n == 0 writes nothing.
+                 the rays; n == 0 writes nothing.  Host-pointer calls of 1, 4096, 4097, 8193 and 1 points at K = 16 on one handle of its
+                 own (its staging is made, kept, grown twice, kept), byte-equal to the device-pointer calls.
   5 invalid      the nine kinds of test_query_gpu._spoil on the point as a ray: K = 16, n = 130 at points 0, 3, 4, 63, 129; K = 128, n = 5
                  at points 0 and 4.
   6 empty world  occluded 0 and bent = the sum of the whole table; 257 copies of one point under S = 1 give 257 equal texels.
@@ -463,3 +464,28 @@ def test_cpp_engine_bakes(built, tmp_path):
     assert r.returncode == 0 and "BAKE DELIVERY OK" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
     out = open(tmp_path / "out.bin", "rb").read()
     assert out == want.tobytes(), "Engine::bakeOcclusion differs from Context.bake_occlusion"
+
+
+GROWTH = (1, 4096, 4097, 8193, 1)      # on one new handle: a staging of 4096 made, kept, grown to 8192, grown to 16 384, kept
+
+
+def test_one_handle_grows_its_staging_twice(sphere):
+    """Host-pointer calls of GROWTH's sizes at K = 16 on one handle of its own: every result equals, byte for byte, the device-pointer call
+    over the same points (the surface points of `inside_sphere`, repeated to 8 193: point i uses set_of(i), so a repeat is another case)."""
+    ctx = sphere[0]
+    points = np.resize(_surface_points(ctx)[1], max(GROWTH))
+    b = bake.Bake(ctx._ctx)
+    ctx.sync()      # (makes the head device the current one for the buffers)
+    d_points, d_texels = _hiprt.DeviceBuffer.of(points), _hiprt.DeviceBuffer(points.size * texel_dtype.itemsize)
+    try:
+        b.set_directions((16, 3))
+        for turn, n in enumerate(GROWTH):
+            got = b.occlusion(points[:n], 7)
+            b.occlusion_device(d_points.ptr, n, d_texels.ptr, 7)
+            ctx.sync()
+            want = d_texels.download((n,), texel_dtype)
+            assert (want["occluded"] <= 16).all() and (n == 1 or 0 < int(want["occluded"].sum()) < 16 * n), n
+            assert got.tobytes() == want.tobytes(), f"turn {turn}, n = {n}: the bake through the staging"
+    finally:
+        d_points.free(), d_texels.free()
+        b.close()

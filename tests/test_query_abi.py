@@ -152,6 +152,8 @@ def _capacity(have, need):
 
 _PAIRS = [(0, 0), (0, 1), (0, 4096), (0, 4097), (4096, 4096), (4096, 4097), (8192, 8193), (8192, 20000), (100, 50), (2**30, 2**30 + 1), (2**31 - 1, 2**31 - 1),
           (2**30 + 5, 2**31 - 1), (2**31 - 2, 2**31 - 1), (3, 2**31 - 1), (65536, 65537), (1, 60000)]
+# of the calls tests/order_host_main.cpp lists, under the query's limit: 2^30 + 1 rays are taken, a null pointer is looked at before the flags
+_REFUSALS = ["none", "none", "null pointer", "unknown flag", "unknown flag", "none", "none", "null pointer", "more than 2^31 - 1 rays"]
 
 
 def test_the_host_unit_as_a_process_of_its_own_under_sanitizers(built, tmp_path):
@@ -162,4 +164,5 @@ def test_the_host_unit_as_a_process_of_its_own_under_sanitizers(built, tmp_path)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = r.stdout.strip().splitlines()
     assert lines[-1] == f"pairs {len(_PAIRS)}" and lines[-2] == "layout 32 48 16 12 16 32 44"
-    assert [int(v) for v in lines[:-2]] == [_capacity(h, n) for h, n in _PAIRS]
+    assert lines[len(_PAIRS):-2] == ["refusal: " + w for w in _REFUSALS]
+    assert [int(v) for v in lines[:len(_PAIRS)]] == [_capacity(h, n) for h, n in _PAIRS]

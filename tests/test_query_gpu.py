@@ -19,8 +19,9 @@ Trees 0 (reference) and 3 (device SAH) unless said otherwise; one Context per ch
   5 invalid     NaN, +-inf, zero direction, far <= near, near < 0 and (without NORMALIZE) a direction of length 2 at lanes 0, 31, 63, 64
                 and the last of 257: each reads INVALID / the miss fields / t = far's bits / occlusion 0, every valid ray reads what it
                 reads without them; n in {0, 1, 63, 64, 65, 257} through device pointers with a sentinel behind n, byte-equal to the
-                host-pointer calls.
-  6 staleness   one Context: after upload_scene(other), after update_instances with a moved instance, after update_triangles + refit and
+                host-pointer calls.  Host-pointer calls of 1, 4096, 4097, 8193 and 1 rays on one handle of its own (its staging is made,
+                kept, grown twice, kept), closest and occluded by turns, byte-equal to the device-pointer calls.
+  6 staleness  one Context: after upload_scene(other), after update_instances with a moved instance, after update_triangles + refit and
                 after rebuild_trees, trace of fixed rays equals a fresh context's on the changed scene and differs from before.  A
                 refitted context numbers scene_triangle by the order IT was given (the first upload's), a fresh one by the changed
                 scene's: compared through the permutation between the two orders.
@@ -559,3 +560,34 @@ def test_cpp_engine_casts_rays(built, tmp_path, normalize):
     assert len(out) == n * (hit_dtype.itemsize + 4)
     assert out[:n * hit_dtype.itemsize] == want_hits.tobytes(), "Engine::castRays differs from Context.trace"
     assert out[n * hit_dtype.itemsize:] == want_occ.tobytes(), "Engine::occluded differs from Context.occluded"
+
+
+GROWTH = (1, 4096, 4097, 8193, 1)      # on one new handle: a staging of 4096 made, kept, grown to 8192, grown to 16 384, kept
+
+
+def test_one_handle_grows_its_staging_twice(shapes_context):
+    """Host-pointer calls of GROWTH's sizes on one handle of its own, closest and occluded taking turns to go first (the out side of the
+    staging is sized for hits; the occlusion words share it): every result equals, byte for byte, the device-pointer call over the same
+    rays.  The rays leave the camera of `inside_sphere` in 8 193 directions of their own, so every one hits."""
+    ctx, pixel = shapes_context
+    d = np.random.default_rng(22).normal(size=(max(GROWTH), 3)).astype(np.float32)
+    d /= np.sqrt((d * d).sum(-1, dtype=np.float32))[:, None]
+    rays = query.rays(pixel["origin"][0], d, pixel["near"][0], pixel["far"][0])
+    q = query.Query(ctx._ctx)
+    ctx.sync()      # (makes the head device the current one for the buffers)
+    d_rays, d_hits, d_occ = _hiprt.DeviceBuffer.of(rays), _hiprt.DeviceBuffer(rays.size * hit_dtype.itemsize), _hiprt.DeviceBuffer(rays.size * 4)
+    try:
+        for turn, n in enumerate(GROWTH):
+            got = {}
+            for call in (q.closest, q.occluded)[::1 if turn % 2 == 0 else -1]:
+                got[call.__name__] = call(rays[:n])
+            q.closest_device(d_rays.ptr, n, d_hits.ptr)
+            q.occluded_device(d_rays.ptr, n, d_occ.ptr)
+            ctx.sync()
+            hits, occ = d_hits.download((n,), hit_dtype), d_occ.download((n,), np.uint32)
+            assert _found(hits).all() and occ.all(), n
+            assert got["closest"].tobytes() == hits.tobytes(), f"turn {turn}, n = {n}: closest through the staging"
+            assert got["occluded"].tobytes() == occ.tobytes(), f"turn {turn}, n = {n}: occluded through the staging"
+    finally:
+        d_rays.free(), d_hits.free(), d_occ.free()
+        q.close()
