@@ -150,6 +150,14 @@ __global__ void __launch_bounds__(256) rz_selftest_div_kernel(uint32_t n_per_thr
                 box_range_pairs(b0, b1, splat_pairs(r), tmin_p, tmax_p);
                 box_range_unpacked<true>(b0, b1, r, tmin_u, tmax_u);
                 if (__float_as_uint(tmin_p) != __float_as_uint(tmin_u) || __float_as_uint(tmax_p) != __float_as_uint(tmax_u)) bad += 1;
+                // ... and the same of the sequences that read the ray by operand select (box_range_sel, RZ_FLAT_SEL_BOXES), called directly
+                // as well.  Origin, direction and reciprocal are nine independent draws, so the two halves of every pair of the ray differ;
+                // the spare half beside y.z is given a number of its own here: an operand read from the wrong half shows.
+                WalkRaySel sp = sel_pairs(r);
+                sp.yz = pk(r.y.z, unit(14) + 2.0f);
+                float tmin_s, tmax_s;
+                box_range_sel(b0, b1, sp, tmin_s, tmax_s);
+                if (__float_as_uint(tmin_s) != __float_as_uint(tmin_u) || __float_as_uint(tmax_s) != __float_as_uint(tmax_u)) bad += 1;
             }
             // the one-leaf walk's triangle loop: two triangles in one iteration (tri_pair_step: tri_hit2 + pair_pick) against the
             // one-by-one loop (tri_hit, the far end moving between the two) — far end, winner, b1, b2 and the facing bit.  Random pairs

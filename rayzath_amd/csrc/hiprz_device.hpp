@@ -36,6 +36,12 @@ namespace hiprz {
 #ifndef RZ_FLAT_PACKED_BOXES   // one-leaf walk (closest_hit_flat): the up-front instance boxes, the root box and the visits' mesh box on register pairs
 #define RZ_FLAT_PACKED_BOXES 0 // off: measured alone it loses 2.1 % on config B, and it takes 2.5 % from the triangle pairs (profiles/r13)
 #endif
+#ifndef RZ_FLAT_SEL_BOXES      // ... the same three box tests on packed sequences that read the ray's own registers by operand select (box_range_sel):
+#define RZ_FLAT_SEL_BOXES 0    // no splat pairs, no negated copies.  off: 279 vector instructions fewer in the flagship kernel and 1.3 – 1.5 % slower on config B (profiles/r23)
+#endif
+#ifndef RZ_FLAT_FULL_LEAF      // one-leaf walk: the up-front tests of a leaf of eight instances as one straight run for a wave of fast rays
+#define RZ_FLAT_FULL_LEAF 1    // on: +1.5 % on config B (profiles/r23)
+#endif
 #ifndef RZ_FLAT_PAIR_TRIS      // one-leaf walk: the triangles of a leaf tested two at a time on float2 vectors (tri_hit2)
 #define RZ_FLAT_PAIR_TRIS 1    // on: +3.9 % on config B measured alone
 #endif
@@ -505,6 +511,14 @@ RZ_DEV void box_range_unpacked(float4 b0, float4 b1, const WalkRay& r, float& tm
     tmin = max_gt(max_gt(min_lt(t1, t2), min_lt(t3, t4)), min_lt(t5, t6));
     tmax = min_lt(min_lt(max_gt(t1, t2), max_gt(t3, t4)), max_gt(t5, t6));
 }
+// the fast branch of box_range_unpacked<true> on its own, for a caller that has asked __all(r.fast) already
+RZ_DEV void box_range_fast(float4 b0, float4 b1, const WalkRay& r, float& tmin, float& tmax) {
+    const float t1 = div_shared(b0.x - r.o.x, r.d.x, r.y.x), t2 = div_shared(b0.y - r.o.x, r.d.x, r.y.x);
+    const float t3 = div_shared(b0.z - r.o.y, r.d.y, r.y.y), t4 = div_shared(b0.w - r.o.y, r.d.y, r.y.y);
+    const float t5 = div_shared(b1.x - r.o.z, r.d.z, r.y.z), t6 = div_shared(b1.y - r.o.z, r.d.z, r.y.z);
+    tmin = vmax3(vmin(t1, t2), vmin(t3, t4), vmin(t5, t6));
+    tmax = vmin3(vmax(t1, t2), vmax(t3, t4), vmax(t5, t6));
+}
 template <bool SHARED_RCP>
 RZ_DEV bool box_hit_unpacked(float4 b0, float4 b1, const WalkRay& r) {
     float tmin, tmax;
@@ -602,10 +616,64 @@ RZ_DEV void box_range_pairs(float4 b0, float4 b1, const WalkRayPairs& p, float& 
     tmin = vmax3(vmin(tx.x, tx.y), vmin(ty.x, ty.y), vmin(tz.x, tz.y));
     tmax = vmin3(vmax(tx.x, tx.y), vmax(ty.x, ty.y), vmax(tz.x, tz.y));
 }
+// The same three sequences WITHOUT splat pairs: a packed fp32 instruction selects, per source operand, which half of the 64-bit register
+// feeds its low result (op_sel) and which its high result (op_sel_hi), and negates a source per half (neg_lo, neg_hi).  So one half of
+// any register pair is broadcast to both results where it is read, and -d never exists as a register: the ray is its own nine values
+// held as five pairs, ten registers where splat_pairs takes eighteen and eighteen moves.
+//   {o.x, o.y}  {o.z, d.x}  {d.y, d.z}  {y.x, y.y}  {y.z, -}
+// — WalkRay's own nine floats two by two, in its own order.  Built where a run of box tests starts and dead where it ends, like
+// WalkRayPairs.  The last half is never selected.  (Of the layouts tried this one leaves the five-wave resident kernel with the least
+// scratch; {o.z, d.z} {d.x, d.y} put a scratch access between the walk's barriers: profiles/r23.)
+// A pair is a 64-bit integer here, not an f2: with float vectors the compiler read a pair's first float together with its neighbour
+// in the ray's struct, as one vector load, and then kept that struct — and the kernel's own ray beside it — in scratch memory.
+typedef uint64_t pk2;
+RZ_DEV pk2 pk(float lo, float hi) { return uint64_t(__float_as_uint(lo)) | (uint64_t(__float_as_uint(hi)) << 32); }
+RZ_DEV float pk_lo(pk2 v) { return __uint_as_float(uint32_t(v)); }
+RZ_DEV float pk_hi(pk2 v) { return __uint_as_float(uint32_t(v >> 32)); }
+struct WalkRaySel {
+    pk2 oxy, ozdx, dyz, yxy, yz;
+};
+RZ_DEV WalkRaySel sel_pairs(const WalkRay& r) {
+    WalkRaySel p;
+    p.oxy = pk(r.o.x, r.o.y), p.ozdx = pk(r.o.z, r.d.x), p.dyz = pk(r.d.y, r.d.z), p.yxy = pk(r.y.x, r.y.y);
+    p.yz = pk(r.y.z, __builtin_nondeterministic_value(r.y.z));  // any register at all: nothing is written to it
+    return p;
+}
+// One axis: both quotients of the box pair b = {min, max} over the ray component in half HO of `o`, HD of `d`, HY of `y` — per result
+// element div_shared's operations in div_shared's order (n = b - o; q = n * y; r = fma(-d, q, n); q = fma(r, y, q); twice).  Inline
+// assembly like vmin / vmax3: the compiler finds the modifiers for its own splats in places, not for these.  UNIFORM_BOX: the box is
+// wave-uniform (the world's root box) and is read from scalar registers where it is, by the one instruction that reads it.
+template <int HO, int HD, int HY, bool UNIFORM_BOX = false>
+RZ_DEV pk2 div_sel(pk2 b, pk2 o, pk2 d, pk2 y) {
+    pk2 n, q, r;
+    if constexpr (UNIFORM_BOX) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,%3] op_sel_hi:[1,%3] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(n) : "s"(b), "v"(o), "n"(HO));
+    else asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,%3] op_sel_hi:[1,%3] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(n) : "v"(b), "v"(o), "n"(HO));
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,%3] op_sel_hi:[1,%3]" : "=v"(q) : "v"(n), "v"(y), "n"(HY));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[%4,0,0] op_sel_hi:[%4,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(r) : "v"(d), "v"(q), "v"(n), "n"(HD));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,%4,0] op_sel_hi:[1,%4,1]" : "=v"(q) : "v"(r), "v"(y), "v"(q), "n"(HY));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[%4,0,0] op_sel_hi:[%4,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(r) : "v"(d), "v"(q), "v"(n), "n"(HD));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,%4,0] op_sel_hi:[1,%4,1]" : "=v"(q) : "v"(r), "v"(y), "v"(q), "n"(HY));
+    return q;
+}
+// one box, the ray given as pairs: box_range_unpacked<true>'s tmin and tmax, bit for bit; r.fast lanes only
+template <bool UNIFORM_BOX = false>
+RZ_DEV void box_range_sel(float4 b0, float4 b1, const WalkRaySel& p, float& tmin, float& tmax) {
+    const pk2 tx = div_sel<0, 1, 0, UNIFORM_BOX>(pk(b0.x, b0.y), p.oxy, p.ozdx, p.yxy);
+    const pk2 ty = div_sel<1, 0, 1, UNIFORM_BOX>(pk(b0.z, b0.w), p.oxy, p.dyz, p.yxy);
+    const pk2 tz = div_sel<0, 1, 0, UNIFORM_BOX>(pk(b1.x, b1.y), p.ozdx, p.dyz, p.yz);
+    tmin = vmax3(vmin(pk_lo(tx), pk_hi(tx)), vmin(pk_lo(ty), pk_hi(ty)), vmin(pk_lo(tz), pk_hi(tz)));
+    tmax = vmin3(vmax(pk_lo(tx), pk_hi(tx)), vmax(pk_lo(ty), pk_hi(ty)), vmax(pk_lo(tz), pk_hi(tz)));
+}
 // box_range_unpacked's tmin and tmax, bit for bit
-template <bool SHARED_RCP>
+template <bool SHARED_RCP, bool UNIFORM_BOX = false>
 RZ_DEV void box_range_packed(float4 b0, float4 b1, const WalkRay& r, float& tmin, float& tmax) {
-#if RZ_FLAT_PACKED_BOXES
+#if RZ_FLAT_SEL_BOXES
+    if (SHARED_RCP && __all(r.fast)) {  // wave-uniform branch
+        box_range_sel<UNIFORM_BOX>(b0, b1, sel_pairs(r), tmin, tmax);
+        return;
+    }
+    box_range_unpacked<false>(b0, b1, r, tmin, tmax);
+#elif RZ_FLAT_PACKED_BOXES
     if (SHARED_RCP && __all(r.fast)) {  // wave-uniform branch
         box_range_pairs(b0, b1, splat_pairs(r), tmin, tmax);
         return;
@@ -615,10 +683,10 @@ RZ_DEV void box_range_packed(float4 b0, float4 b1, const WalkRay& r, float& tmin
     box_range_unpacked<SHARED_RCP>(b0, b1, r, tmin, tmax);
 #endif
 }
-template <bool SHARED_RCP>
+template <bool SHARED_RCP, bool UNIFORM_BOX = false>
 RZ_DEV bool box_hit_packed(float4 b0, float4 b1, const WalkRay& r) {
     float tmin, tmax;
-    box_range_packed<SHARED_RCP>(b0, b1, r, tmin, tmax);
+    box_range_packed<SHARED_RCP, UNIFORM_BOX>(b0, b1, r, tmin, tmax);
     return !(tmax < r.near_ || tmin > tmax || tmin > r.far_);
 }
 
@@ -971,6 +1039,26 @@ RZ_DEV FlatWorld make_flat_world(const DScene& s) {
 template <bool COUNT, bool RCP>
 RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, const WalkRay& g, float (&tm)[8], bool counting, Counters& cnt) {
     uint32_t mask = 0u;
+#if RZ_FLAT_SEL_BOXES
+    // the ray's five pairs stand for the eight boxes and end with them; the loop keeps the shape it has without the switch (one loop, the
+    // wave-uniform choice inside it): with a loop per form the slots' tm[] moved from register to register between the boxes
+    const WalkRaySel gp = sel_pairs(g);
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; ++k) {
+        tm[k] = 0.0f;
+        if (k < fw.count) {  // scalar
+            float4 ib0, ib1;
+            load_instance_box(s, flat_id(fw.ids, k), ib0, ib1);
+            float tmin, tmax;
+            if (RCP && __all(g.fast)) box_range_sel(ib0, ib1, gp, tmin, tmax);  // wave-uniform branch
+            else box_range_unpacked<false>(ib0, ib1, g, tmin, tmax);
+            if (counting) { RZ_PHASE(1); RZ_COUNT(box_tests); }
+            mask |= uint32_t(!(tmax < g.near_ || tmin > tmax)) << k;
+            tm[k] = tmin;
+        }
+    }
+    return mask;
+#else
 #if RZ_FLAT_PACKED_BOXES
     if (RCP && __all(g.fast)) {  // wave-uniform branch: the ray's pairs are built once for the eight boxes and end with them
         const WalkRayPairs gp = splat_pairs(g);
@@ -990,6 +1078,23 @@ RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, con
         return mask;
     }
 #endif
+#if RZ_FLAT_FULL_LEAF
+    // A full leaf (a Cornell box) under a wave of fast rays: its eight tests as one straight run, no `k < count` and no choice of form
+    // between the slots — at every such join the compiler moved the slots' tm[] from register to register (profiles/r23)
+    if (fw.count == 8u && RCP && __all(g.fast)) {  // scalar, wave-uniform
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            float4 ib0, ib1;
+            load_instance_box(s, flat_id(fw.ids, k), ib0, ib1);
+            float tmin, tmax;
+            box_range_fast(ib0, ib1, g, tmin, tmax);
+            if (counting) { RZ_PHASE(1); RZ_COUNT(box_tests); }
+            mask |= uint32_t(!(tmax < g.near_ || tmin > tmax)) << k;
+            tm[k] = tmin;
+        }
+        return mask;
+    }
+#endif
 #pragma unroll
     for (uint32_t k = 0; k < 8u; ++k) {
         tm[k] = 0.0f;
@@ -1004,6 +1109,7 @@ RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, con
         }
     }
     return mask;
+#endif
 }
 
 // C of a binned round for closest_hit_flat: the lane that holds dense item `slot` enters the item's instance for the item's ray.
@@ -1394,7 +1500,7 @@ __device__ __forceinline__ int closest_hit_flat(const DScene& s, const FlatWorld
     if (active) {
         RZ_PHASE(0);
         RZ_COUNT(box_tests);
-        if (box_hit_packed<RCP>(fw.root0, fw.root1, g)) flat_mask = pretest_leaf_instances<COUNT, RCP>(s, fw, g, tm, true, cnt);
+        if (box_hit_packed<RCP, true>(fw.root0, fw.root1, g)) flat_mask = pretest_leaf_instances<COUNT, RCP>(s, fw, g, tm, true, cnt);
         else root_missed = true;
     }
     // both halves of the double-buffered bins: the round that left the previous call found its own half empty and left the other one,
