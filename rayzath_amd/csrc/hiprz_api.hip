@@ -140,25 +140,8 @@ __global__ void __launch_bounds__(256) rz_selftest_div_kernel(uint32_t n_per_thr
                 if ((hit && !exact) || (missed && exact) || (hit && missed)) bad += 1;
                 if (!hit && !missed) undecided += 1;
             }
-            // (The two comparisons below run on every case and report into `bad`; `tested` stays the count of quotients and filtered box
+            // (The comparison below runs on every case and reports into `bad`; `tested` stays the count of quotients and filtered box
             // tests, which tests/test_parity_gpu.py bounds from both sides.)
-            // the one-leaf walk's packed box test (RZ_FLAT_PACKED_BOXES): tmin and tmax of the packed sequences (box_range_pairs, what
-            // box_range_packed runs for a wave of fast rays) are box_range_unpacked's, bit for bit.  Called directly, so that the comparison
-            // is there whichever way the switch stands; a ray that is not fast takes box_range_unpacked<false> under either setting.
-            if (r.fast) {
-                float tmin_p, tmax_p, tmin_u, tmax_u;
-                box_range_pairs(b0, b1, splat_pairs(r), tmin_p, tmax_p);
-                box_range_unpacked<true>(b0, b1, r, tmin_u, tmax_u);
-                if (__float_as_uint(tmin_p) != __float_as_uint(tmin_u) || __float_as_uint(tmax_p) != __float_as_uint(tmax_u)) bad += 1;
-                // ... and the same of the sequences that read the ray by operand select (box_range_sel, RZ_FLAT_SEL_BOXES), called directly
-                // as well.  Origin, direction and reciprocal are nine independent draws, so the two halves of every pair of the ray differ;
-                // the spare half beside y.z is given a number of its own here: an operand read from the wrong half shows.
-                WalkRaySel sp = sel_pairs(r);
-                sp.yz = pk(r.y.z, unit(14) + 2.0f);
-                float tmin_s, tmax_s;
-                box_range_sel(b0, b1, sp, tmin_s, tmax_s);
-                if (__float_as_uint(tmin_s) != __float_as_uint(tmin_u) || __float_as_uint(tmax_s) != __float_as_uint(tmax_u)) bad += 1;
-            }
             // the one-leaf walk's triangle loop: two triangles in one iteration (tri_pair_step: tri_hit2 + pair_pick) against the
             // one-by-one loop (tri_hit, the far end moving between the two) — far end, winner, b1, b2 and the facing bit.  Random pairs
             // in front of the ray, and by the bits of `kind`: the same triangle twice (equal distances: the first wins), a ray almost in
@@ -214,34 +197,10 @@ __global__ void __launch_bounds__(256) rz_selftest_div_kernel(uint32_t n_per_thr
                 // as a pair
                 LeafBest best;
                 best.far_ = q.far_, best.triangle = 0xFFFFFFFFu, best.b1 = best.b2 = 0.0f, best.external = false;
-                tri_pair_step(ta[0], ta[1], ta[2], has_b ? tb[0] : ta[0], has_b ? tb[1] : ta[1], has_b ? tb[2] : ta[2], 0u, has_b ? 1u : 0u, has_b, q, best);
+                tri_pair_step(pair3(ta[0], has_b ? tb[0] : ta[0]), pair3(ta[1], has_b ? tb[1] : ta[1]), pair3(ta[2], has_b ? tb[2] : ta[2]), 0u, has_b, q, best);
                 if (__float_as_uint(best.far_) != __float_as_uint(seq.far_) || best.triangle != seq_tri || __float_as_uint(best.b1) != __float_as_uint(seq_b1) ||
                     __float_as_uint(best.b2) != __float_as_uint(seq_b2) || best.external != seq_external)
                     bad += 1;
-            }
-            // tri_hit2's two reciprocals as one sequence (rcp_pair, RZ_FLAT_PK_DIV) against `1.0f / x`, bit for bit (a NaN for a NaN).  Called
-            // directly, whichever way the switch stands.  By the bits of `sel`: any bit pattern at all; a determinant the nudge has
-            // lifted (0 < x < 2e-7) or one just outside it; an x whose reciprocal is denormal or rounds to the largest finite values
-            // (|x| >= 2^126); a denormal or tiny x (the reciprocal overflows or nearly does); +-0, +-inf and NaNs.
-            {
-                auto operand = [&](uint32_t k) {
-                    const uint32_t w = mix32(h + 0x51EDu * k), sel = (w >> 3) & 7u, sign = w & 0x80000000u, frac = mix32(w) & 0x7FFFFFu;
-                    if (sel == 0u) return __uint_as_float(mix32(w ^ 0x3C6EF372u));
-                    if (sel == 1u) return unit(50u + k) * 2.0e-7f;
-                    if (sel == 2u) return __uint_as_float(sign | __float_as_uint(1.0e-7f + (unit(52u + k) - 0.5f) * 1.0e-9f));
-                    if (sel == 3u) return __uint_as_float(sign | ((253u + (w >> 8) % 2u) << 23) | frac);
-                    if (sel == 4u) return __uint_as_float(sign | (((w >> 8) % 3u) << 23) | frac);
-                    if (sel == 5u) {
-                        const uint32_t special[4] = {0x00000000u, 0x7F800000u, 0x7FC00000u | frac, 0x7F800001u};
-                        return __uint_as_float(sign | special[(w >> 8) & 3u]);
-                    }
-                    return __uint_as_float(sign | ((64u + (w >> 8) % 128u) << 23) | frac);  // ordinary magnitudes, 2^-63 .. 2^64
-                };
-                const f2 x = {operand(1u), operand(2u)};
-                const f2 got = rcp_pair(x);
-                const float want_x = 1.0f / x.x, want_y = 1.0f / x.y;
-                if (__float_as_uint(got.x) != __float_as_uint(want_x) && !(got.x != got.x && want_x != want_x)) bad += 1;
-                if (__float_as_uint(got.y) != __float_as_uint(want_y) && !(got.y != got.y && want_y != want_y)) bad += 1;
             }
         }
     }

@@ -33,24 +33,6 @@ namespace hiprz {
 #ifndef RZ_BATCH_SHARED_RCP   // ... in the resident pipeline's batch kernel
 #define RZ_BATCH_SHARED_RCP 1
 #endif
-#ifndef RZ_FLAT_PACKED_BOXES   // one-leaf walk (closest_hit_flat): the up-front instance boxes, the root box and the visits' mesh box on register pairs
-#define RZ_FLAT_PACKED_BOXES 0 // off: measured alone it loses 2.1 % on config B, and it takes 2.5 % from the triangle pairs (profiles/r13)
-#endif
-#ifndef RZ_FLAT_SEL_BOXES      // ... the same three box tests on packed sequences that read the ray's own registers by operand select (box_range_sel):
-#define RZ_FLAT_SEL_BOXES 0    // no splat pairs, no negated copies.  off: 279 vector instructions fewer in the flagship kernel and 1.3 – 1.5 % slower on config B (profiles/r23)
-#endif
-#ifndef RZ_FLAT_FULL_LEAF      // one-leaf walk: the up-front tests of a leaf of eight instances as one straight run for a wave of fast rays
-#define RZ_FLAT_FULL_LEAF 1    // on: +1.5 % on config B (profiles/r23)
-#endif
-#ifndef RZ_FLAT_PAIR_TRIS      // one-leaf walk: the triangles of a leaf tested two at a time on float2 vectors (tri_hit2)
-#define RZ_FLAT_PAIR_TRIS 1    // on: +3.9 % on config B measured alone
-#endif
-#ifndef RZ_FLAT_PAIR_RECORDS   // ... read from pair records (the two triangles interleaved: one address, loads in operand order) instead of two 48-byte records
-#define RZ_FLAT_PAIR_RECORDS 1 // on: +2.7 % on config B measured alone (profiles/r14)
-#endif
-#ifndef RZ_FLAT_PK_DIV         // ... and tri_hit2's two true divisions as ONE sequence, its six plain operations packed (rcp_pair)
-#define RZ_FLAT_PK_DIV 0       // off: on top of the records it takes 0.5 % back, alone the five-wave build spills inside the walk (-17.7 %)
-#endif
 #ifndef RZ_MIRROR_LOBE_CONST   // sample_direction: a glossy lobe of roughness +-0 takes (sin, cos) = (+0, 1), the constants its powf, acosf and sincosf return
 #define RZ_MIRROR_LOBE_CONST 1
 #endif
@@ -587,108 +569,9 @@ RZ_DEV bool tri_hit(v3 v1, v3 edge1, v3 edge2, const WalkRay& r, float& t, float
 
 // ---- packed forms for the one-leaf walk (closest_hit_flat): two IEEE fp32 operations per lane and instruction ----
 // v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 round each half exactly like their one-float twins, and -ffp-contract=off keeps every
-// multiply and add apart: a packed sequence is the unpacked one, twice.  hiprz_selftest compares both forms below bit for bit.
-
-// The ray of a box test as register pairs (origin, negated direction, refined reciprocal, each splat): built where a run of box tests
-// starts and dead where it ends — the pairs are 18 registers that must not live across a round.
-struct WalkRayPairs {
-    f2 ox, oy, oz, ndx, ndy, ndz, yx, yy, yz;
-};
-RZ_DEV WalkRayPairs splat_pairs(const WalkRay& r) {
-    WalkRayPairs p;
-    p.ox = f2{r.o.x, r.o.x}, p.oy = f2{r.o.y, r.o.y}, p.oz = f2{r.o.z, r.o.z};
-    p.ndx = f2{-r.d.x, -r.d.x}, p.ndy = f2{-r.d.y, -r.d.y}, p.ndz = f2{-r.d.z, -r.d.z};
-    p.yx = f2{r.y.x, r.y.x}, p.yy = f2{r.y.y, r.y.y}, p.yz = f2{r.y.z, r.y.z};
-    return p;
-}
-RZ_DEV f2 div_pairs(f2 n, f2 nd, f2 yy) {  // div_shared2 on pairs that exist already
-    f2 q = n * yy;
-    f2 r = __builtin_elementwise_fma(nd, q, n);
-    q = __builtin_elementwise_fma(r, yy, q);
-    r = __builtin_elementwise_fma(nd, q, n);
-    return __builtin_elementwise_fma(r, yy, q);
-}
-// the fast path of box_range_unpacked, its six quotients as three packed sequences (box_hit's): r.fast lanes only
-RZ_DEV void box_range_pairs(float4 b0, float4 b1, const WalkRayPairs& p, float& tmin, float& tmax) {
-    const f2 tx = div_pairs(f2{b0.x, b0.y} - p.ox, p.ndx, p.yx);
-    const f2 ty = div_pairs(f2{b0.z, b0.w} - p.oy, p.ndy, p.yy);
-    const f2 tz = div_pairs(f2{b1.x, b1.y} - p.oz, p.ndz, p.yz);
-    tmin = vmax3(vmin(tx.x, tx.y), vmin(ty.x, ty.y), vmin(tz.x, tz.y));
-    tmax = vmin3(vmax(tx.x, tx.y), vmax(ty.x, ty.y), vmax(tz.x, tz.y));
-}
-// The same three sequences WITHOUT splat pairs: a packed fp32 instruction selects, per source operand, which half of the 64-bit register
-// feeds its low result (op_sel) and which its high result (op_sel_hi), and negates a source per half (neg_lo, neg_hi).  So one half of
-// any register pair is broadcast to both results where it is read, and -d never exists as a register: the ray is its own nine values
-// held as five pairs, ten registers where splat_pairs takes eighteen and eighteen moves.
-//   {o.x, o.y}  {o.z, d.x}  {d.y, d.z}  {y.x, y.y}  {y.z, -}
-// — WalkRay's own nine floats two by two, in its own order.  Built where a run of box tests starts and dead where it ends, like
-// WalkRayPairs.  The last half is never selected.  (Of the layouts tried this one leaves the five-wave resident kernel with the least
-// scratch; {o.z, d.z} {d.x, d.y} put a scratch access between the walk's barriers: profiles/r23.)
-// A pair is a 64-bit integer here, not an f2: with float vectors the compiler read a pair's first float together with its neighbour
-// in the ray's struct, as one vector load, and then kept that struct — and the kernel's own ray beside it — in scratch memory.
-typedef uint64_t pk2;
-RZ_DEV pk2 pk(float lo, float hi) { return uint64_t(__float_as_uint(lo)) | (uint64_t(__float_as_uint(hi)) << 32); }
-RZ_DEV float pk_lo(pk2 v) { return __uint_as_float(uint32_t(v)); }
-RZ_DEV float pk_hi(pk2 v) { return __uint_as_float(uint32_t(v >> 32)); }
-struct WalkRaySel {
-    pk2 oxy, ozdx, dyz, yxy, yz;
-};
-RZ_DEV WalkRaySel sel_pairs(const WalkRay& r) {
-    WalkRaySel p;
-    p.oxy = pk(r.o.x, r.o.y), p.ozdx = pk(r.o.z, r.d.x), p.dyz = pk(r.d.y, r.d.z), p.yxy = pk(r.y.x, r.y.y);
-    p.yz = pk(r.y.z, __builtin_nondeterministic_value(r.y.z));  // any register at all: nothing is written to it
-    return p;
-}
-// One axis: both quotients of the box pair b = {min, max} over the ray component in half HO of `o`, HD of `d`, HY of `y` — per result
-// element div_shared's operations in div_shared's order (n = b - o; q = n * y; r = fma(-d, q, n); q = fma(r, y, q); twice).  Inline
-// assembly like vmin / vmax3: the compiler finds the modifiers for its own splats in places, not for these.  UNIFORM_BOX: the box is
-// wave-uniform (the world's root box) and is read from scalar registers where it is, by the one instruction that reads it.
-template <int HO, int HD, int HY, bool UNIFORM_BOX = false>
-RZ_DEV pk2 div_sel(pk2 b, pk2 o, pk2 d, pk2 y) {
-    pk2 n, q, r;
-    if constexpr (UNIFORM_BOX) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,%3] op_sel_hi:[1,%3] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(n) : "s"(b), "v"(o), "n"(HO));
-    else asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,%3] op_sel_hi:[1,%3] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(n) : "v"(b), "v"(o), "n"(HO));
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,%3] op_sel_hi:[1,%3]" : "=v"(q) : "v"(n), "v"(y), "n"(HY));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[%4,0,0] op_sel_hi:[%4,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(r) : "v"(d), "v"(q), "v"(n), "n"(HD));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,%4,0] op_sel_hi:[1,%4,1]" : "=v"(q) : "v"(r), "v"(y), "v"(q), "n"(HY));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[%4,0,0] op_sel_hi:[%4,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "=v"(r) : "v"(d), "v"(q), "v"(n), "n"(HD));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,%4,0] op_sel_hi:[1,%4,1]" : "=v"(q) : "v"(r), "v"(y), "v"(q), "n"(HY));
-    return q;
-}
-// one box, the ray given as pairs: box_range_unpacked<true>'s tmin and tmax, bit for bit; r.fast lanes only
-template <bool UNIFORM_BOX = false>
-RZ_DEV void box_range_sel(float4 b0, float4 b1, const WalkRaySel& p, float& tmin, float& tmax) {
-    const pk2 tx = div_sel<0, 1, 0, UNIFORM_BOX>(pk(b0.x, b0.y), p.oxy, p.ozdx, p.yxy);
-    const pk2 ty = div_sel<1, 0, 1, UNIFORM_BOX>(pk(b0.z, b0.w), p.oxy, p.dyz, p.yxy);
-    const pk2 tz = div_sel<0, 1, 0, UNIFORM_BOX>(pk(b1.x, b1.y), p.ozdx, p.dyz, p.yz);
-    tmin = vmax3(vmin(pk_lo(tx), pk_hi(tx)), vmin(pk_lo(ty), pk_hi(ty)), vmin(pk_lo(tz), pk_hi(tz)));
-    tmax = vmin3(vmax(pk_lo(tx), pk_hi(tx)), vmax(pk_lo(ty), pk_hi(ty)), vmax(pk_lo(tz), pk_hi(tz)));
-}
-// box_range_unpacked's tmin and tmax, bit for bit
-template <bool SHARED_RCP, bool UNIFORM_BOX = false>
-RZ_DEV void box_range_packed(float4 b0, float4 b1, const WalkRay& r, float& tmin, float& tmax) {
-#if RZ_FLAT_SEL_BOXES
-    if (SHARED_RCP && __all(r.fast)) {  // wave-uniform branch
-        box_range_sel<UNIFORM_BOX>(b0, b1, sel_pairs(r), tmin, tmax);
-        return;
-    }
-    box_range_unpacked<false>(b0, b1, r, tmin, tmax);
-#elif RZ_FLAT_PACKED_BOXES
-    if (SHARED_RCP && __all(r.fast)) {  // wave-uniform branch
-        box_range_pairs(b0, b1, splat_pairs(r), tmin, tmax);
-        return;
-    }
-    box_range_unpacked<false>(b0, b1, r, tmin, tmax);
-#else
-    box_range_unpacked<SHARED_RCP>(b0, b1, r, tmin, tmax);
-#endif
-}
-template <bool SHARED_RCP, bool UNIFORM_BOX = false>
-RZ_DEV bool box_hit_packed(float4 b0, float4 b1, const WalkRay& r) {
-    float tmin, tmax;
-    box_range_packed<SHARED_RCP, UNIFORM_BOX>(b0, b1, r, tmin, tmax);
-    return !(tmax < r.near_ || tmin > tmax || tmin > r.far_);
-}
+// multiply and add apart: a packed sequence is the unpacked one, twice.  Only the triangles take this form (+3.9 % on config B measured
+// alone, profiles/r13); the box tests stay on box_range_unpacked: on splat register pairs they lost 2.1 % (profiles/r13), read by operand
+// select 1.3 - 1.5 % (profiles/r23).  DESIGN.md §9 names the commits that hold those variants.
 
 // Moller-Trumbore on two triangles at once: element 0 = triangle a, element 1 = triangle b of the same leaf, against the same ray.
 // Every element performs tri_hit's operations in tri_hit's order — the det nudge element by element, two true divisions — except that
@@ -698,36 +581,14 @@ struct v3p {
     f2 x, y, z;
 };
 RZ_DEV v3p pair3(float4 a, float4 b) { return v3p{f2{a.x, b.x}, f2{a.y, b.y}, f2{a.z, b.z}}; }
-// {1.0f / x.x, 1.0f / x.y}: the compiler's own expansion of the correctly rounded `1.0f / x`, operation for operation and in its order —
-// v_div_scale twice, v_rcp, six fused or plain operations, v_div_fmas, v_div_fixup — with the six in the middle, which are plain IEEE
-// operations, on both elements at once.  Nothing is removed or reordered: this is not a shorter division.  hiprz_selftest compares it
-// with `/` bit for bit.
-RZ_DEV f2 rcp_pair(f2 x) {
-    bool scaled_x, scaled_y, unused;
-    const f2 den = {__builtin_amdgcn_div_scalef(1.0f, x.x, false, &unused), __builtin_amdgcn_div_scalef(1.0f, x.y, false, &unused)};
-    const f2 num = {__builtin_amdgcn_div_scalef(1.0f, x.x, true, &scaled_x), __builtin_amdgcn_div_scalef(1.0f, x.y, true, &scaled_y)};
-    const f2 rcp = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-    const f2 nden = -den, one = {1.0f, 1.0f};
-    const f2 e0 = __builtin_elementwise_fma(nden, rcp, one);
-    const f2 r1 = __builtin_elementwise_fma(e0, rcp, rcp);
-    const f2 q0 = num * r1;
-    const f2 e1 = __builtin_elementwise_fma(nden, q0, num);
-    const f2 q1 = __builtin_elementwise_fma(e1, r1, q0);
-    const f2 e2 = __builtin_elementwise_fma(nden, q1, num);
-    return f2{__builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e2.x, r1.x, q1.x, scaled_x), x.x, 1.0f),
-              __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e2.y, r1.y, q1.y, scaled_y), x.y, 1.0f)};
-}
 RZ_DEV float det_nudge(float det) { return float(uint32_t(det > -1.0e-7f) & uint32_t(det < 1.0e-7f)) * 1.0e-7f; }
 RZ_DEV void tri_hit2(v3p v1, v3p edge1, v3p edge2, const WalkRay& r, bool& inside_a, bool& inside_b, f2& t_out, f2& b1_out, f2& b2_out, f2& det_out) {
     const f2 dx = {r.d.x, r.d.x}, dy = {r.d.y, r.d.y}, dz = {r.d.z, r.d.z};
     const v3p pvec = {dy * edge2.z - dz * edge2.y, dz * edge2.x - dx * edge2.z, dx * edge2.y - dy * edge2.x};
     f2 det = edge1.x * pvec.x + edge1.y * pvec.y + edge1.z * pvec.z;
     det = det + f2{det_nudge(det.x), det_nudge(det.y)};
-#if RZ_FLAT_PK_DIV
-    const f2 inv_det = rcp_pair(det);
-#else
+    // two true divisions: as ONE packed sequence they took 0.5 % back on top of the pair records, alone 17.7 % (profiles/r14)
     const f2 inv_det = {1.0f / det.x, 1.0f / det.y};
-#endif
     const v3p tvec = {f2{r.o.x, r.o.x} - v1.x, f2{r.o.y, r.o.y} - v1.y, f2{r.o.z, r.o.z} - v1.z};
     const f2 b1 = (tvec.x * pvec.x + tvec.y * pvec.y + tvec.z * pvec.z) * inv_det;
     const v3p qvec = {tvec.y * edge1.z - tvec.z * edge1.y, tvec.z * edge1.x - tvec.x * edge1.z, tvec.x * edge1.y - tvec.y * edge1.x};
@@ -746,24 +607,8 @@ struct LeafBest {
     float b1, b2;
     bool external;
 };
-// One iteration of a leaf's loop on triangles ia and ib (records a*, b*; ib stands behind ia in leaf order and only counts where
-// has_b): what two iterations of the one-by-one loop leave in `best`.
-RZ_DEV void tri_pair_step(float4 a0, float4 a1, float4 a2, float4 b0, float4 b1, float4 b2, uint32_t ia, uint32_t ib, bool has_b,
-                          const WalkRay& r, LeafBest& best) {
-    f2 t, u, v, det;
-    bool inside_a, inside_b;
-    tri_hit2(pair3(a0, b0), pair3(a1, b1), pair3(a2, b2), r, inside_a, inside_b, t, u, v, det);
-    const PairPick pick = pair_pick(inside_a, inside_b && has_b, t.x, t.y, best.far_);
-    best.far_ = pick.far_;
-    if (pick.winner != 0u) {
-        const bool second = pick.winner == 2u;
-        best.triangle = second ? ib : ia;
-        best.b1 = second ? u.y : u.x, best.b2 = second ? v.y : v.x;
-        best.external = (second ? det.y : det.x) > 0.0f;
-    }
-}
-// ... on a pair record's operands: triangles ia and ia + 1.  (A function of its own, and the one above left as it was: routed through
-// this one, the loop on 48-byte records came out of the compiler with four selects in another order.)
+// One iteration of a leaf's loop on a pair record's operands, triangles ia and ia + 1 (the second only counts where has_b): what two
+// iterations of the one-by-one loop leave in `best`.
 RZ_DEV void tri_pair_step(v3p v1, v3p edge1, v3p edge2, uint32_t ia, bool has_b, const WalkRay& r, LeafBest& best) {
     f2 t, u, v, det;
     bool inside_a, inside_b;
@@ -1039,48 +884,8 @@ RZ_DEV FlatWorld make_flat_world(const DScene& s) {
 template <bool COUNT, bool RCP>
 RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, const WalkRay& g, float (&tm)[8], bool counting, Counters& cnt) {
     uint32_t mask = 0u;
-#if RZ_FLAT_SEL_BOXES
-    // the ray's five pairs stand for the eight boxes and end with them; the loop keeps the shape it has without the switch (one loop, the
-    // wave-uniform choice inside it): with a loop per form the slots' tm[] moved from register to register between the boxes
-    const WalkRaySel gp = sel_pairs(g);
-#pragma unroll
-    for (uint32_t k = 0; k < 8u; ++k) {
-        tm[k] = 0.0f;
-        if (k < fw.count) {  // scalar
-            float4 ib0, ib1;
-            load_instance_box(s, flat_id(fw.ids, k), ib0, ib1);
-            float tmin, tmax;
-            if (RCP && __all(g.fast)) box_range_sel(ib0, ib1, gp, tmin, tmax);  // wave-uniform branch
-            else box_range_unpacked<false>(ib0, ib1, g, tmin, tmax);
-            if (counting) { RZ_PHASE(1); RZ_COUNT(box_tests); }
-            mask |= uint32_t(!(tmax < g.near_ || tmin > tmax)) << k;
-            tm[k] = tmin;
-        }
-    }
-    return mask;
-#else
-#if RZ_FLAT_PACKED_BOXES
-    if (RCP && __all(g.fast)) {  // wave-uniform branch: the ray's pairs are built once for the eight boxes and end with them
-        const WalkRayPairs gp = splat_pairs(g);
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; ++k) {
-            tm[k] = 0.0f;
-            if (k < fw.count) {  // scalar
-                float4 ib0, ib1;
-                load_instance_box(s, flat_id(fw.ids, k), ib0, ib1);
-                float tmin, tmax;
-                box_range_pairs(ib0, ib1, gp, tmin, tmax);
-                if (counting) { RZ_PHASE(1); RZ_COUNT(box_tests); }
-                mask |= uint32_t(!(tmax < g.near_ || tmin > tmax)) << k;
-                tm[k] = tmin;
-            }
-        }
-        return mask;
-    }
-#endif
-#if RZ_FLAT_FULL_LEAF
     // A full leaf (a Cornell box) under a wave of fast rays: its eight tests as one straight run, no `k < count` and no choice of form
-    // between the slots — at every such join the compiler moved the slots' tm[] from register to register (profiles/r23)
+    // between the slots — at every such join the compiler moved the slots' tm[] from register to register (+1.5 % on config B, profiles/r23)
     if (fw.count == 8u && RCP && __all(g.fast)) {  // scalar, wave-uniform
 #pragma unroll
         for (uint32_t k = 0; k < 8u; ++k) {
@@ -1094,7 +899,6 @@ RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, con
         }
         return mask;
     }
-#endif
 #pragma unroll
     for (uint32_t k = 0; k < 8u; ++k) {
         tm[k] = 0.0f;
@@ -1102,14 +906,13 @@ RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, con
             float4 ib0, ib1;
             load_instance_box(s, flat_id(fw.ids, k), ib0, ib1);
             float tmin, tmax;
-            box_range_unpacked<RZ_FLAT_PACKED_BOXES ? false : RCP>(ib0, ib1, g, tmin, tmax);
+            box_range_unpacked<RCP>(ib0, ib1, g, tmin, tmax);
             if (counting) { RZ_PHASE(1); RZ_COUNT(box_tests); }
             mask |= uint32_t(!(tmax < g.near_ || tmin > tmax)) << k;
             tm[k] = tmin;
         }
     }
     return mask;
-#endif
 }
 
 // C of a binned round for closest_hit_flat: the lane that holds dense item `slot` enters the item's instance for the item's ray.
@@ -1126,27 +929,26 @@ RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_c
     const InstanceXform x = load_instance_xform(s, inst);
     WalkRay lr;
     const float len = to_local<RCP>(x, w, lr, scene_fast);
-#if RZ_FLAT_PAIR_TRIS
-    // A mesh that is one leaf, whether 8 lanes share the visit or one lane has it: ONE loop, two triangles per iteration (tri_pair_step).
-    // Lane j of an octet pairs triangles (i, i + 8) from i = j on in steps of 16; a lane on its own pairs (i, i + 1).  The second of a
-    // pair stands behind the first in leaf order, and a lane's pairs follow one another in leaf order: the lane ends with what the
-    // one-by-one loop over its triangles ends with, and an octet's lanes are merged as before.
+    // A mesh that is one leaf, whether 8 lanes share the visit or one lane has it: ONE loop, two triangles per iteration (tri_pair_step:
+    // +3.9 % on config B measured alone, profiles/r13).  The second of a pair stands behind the first in leaf order, and a lane's pairs
+    // follow one another in leaf order: the lane ends with what the one-by-one loop over its triangles ends with, and an octet's lanes
+    // are merged on the nearest hit.
     const float4 n0 = s.nodes[2 * x.blas_root], n1 = s.nodes[2 * x.blas_root + 1];
     const bool wide = (item & RZ_BIN_WIDE) != 0u;
     if (wide || (__float_as_uint(n1.w) & HIPRZ_NODE_LEAF) != 0u) {
-        const uint32_t j = wide ? slot & 7u : 0u, partner = wide ? 8u : 1u;
+        const uint32_t j = wide ? slot & 7u : 0u;
         RZ_PHASE(3);
         if (j == 0u) { RZ_COUNT(box_tests); }  // once per visit
         LeafBest best;
         best.far_ = lr.far_, best.triangle = 0xFFFFFFFFu, best.b1 = best.b2 = 0.0f, best.external = false;
-        if (box_hit_packed<RCP>(n0, n1, lr)) {
+        if (box_hit_unpacked<RCP>(n0, n1, lr)) {
             const uint32_t begin = __float_as_uint(n1.z), end = begin + (__float_as_uint(n1.w) & HIPRZ_NODE_COUNT_MASK);
-#if RZ_FLAT_PAIR_RECORDS
             // Pair record p of the leaf holds its triangles 2p and 2p + 1, interleaved: one address, nine 8-byte values in five reads,
             // and the registers are tri_hit2's operands as they arrive.  A lane on its own takes p = 0, 1, ...; lane j of an octet p = j,
             // j + 8, ... — it pairs (i, i + 1) like a lone lane (a 12-triangle cube is one trip of lanes 0..5).  A lane's pairs still follow
             // one another in leaf order, and octet_min below merges on (distance, triangle): the nearest hit, the first in leaf order among
-            // equals, whatever the partition.  The b half of an odd leaf's last record repeats a and is masked by has_b.
+            // equals, whatever the partition.  The b half of an odd leaf's last record repeats a and is masked by has_b.  (+2.7 % on config B
+            // over the same loop on two 48-byte records, measured alone: profiles/r14.)
             const uint32_t count = end - begin, n_pairs = (count + 1u) >> 1;
             const unsigned char* section = pair_section(s);
             const float2* rec = reinterpret_cast<const float2*>(section + 8u * reinterpret_cast<const uint16_t*>(section)[inst]);
@@ -1160,18 +962,6 @@ RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_c
                 tri_pair_step(v3p{f2{v1x.x, v1x.y}, f2{v1y.x, v1y.y}, f2{v1z.x, v1z.y}}, v3p{f2{e1x.x, e1x.y}, f2{e1y.x, e1y.y}, f2{e1z.x, e1z.y}},
                               v3p{f2{e2x.x, e2x.y}, f2{e2y.x, e2y.y}, f2{e2z.x, e2z.y}}, i, has_b, lr, best);
             }
-            (void)partner;
-#else
-            for (uint32_t i = begin + j; i < end; i += 2u * partner) {
-                const bool has_b = i + partner < end;
-                const uint32_t ib = has_b ? i + partner : i;  // (a lone triangle is loaded twice: no record past the leaf is touched)
-                const float4 a0 = s.tris[3 * i], a1 = s.tris[3 * i + 1], a2 = s.tris[3 * i + 2];
-                const float4 b0 = s.tris[3 * ib], b1 = s.tris[3 * ib + 1], b2 = s.tris[3 * ib + 2];
-                RZ_PHASE(4);
-                if constexpr (COUNT) cnt.tri_tests += has_b ? 2u : 1u;
-                tri_pair_step(a0, a1, a2, b0, b1, b2, i, ib, has_b, lr, best);
-            }
-#endif
         }
         bool mine = best.triangle != 0xFFFFFFFFu;
         if (wide) {
@@ -1194,58 +984,16 @@ RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_c
         }
         return;
     }
-#endif
-    if (item & RZ_BIN_WIDE) {
-        // the mesh is one leaf: its box once per visit (counted by lane 0 of the octet), then this lane's share of its triangles —
-        // each against the range the visit started with, shortened by this lane's own earlier hits; the octet's minimum below is
-        // what the one-by-one loop ends with (the nearest hit, the first in leaf order among equal distances)
-        const uint32_t j = slot & 7u;
-        const float4 n0 = s.nodes[2 * x.blas_root], n1 = s.nodes[2 * x.blas_root + 1];
-        RZ_PHASE(3);
-        if (j == 0u) { RZ_COUNT(box_tests); }
-        uint32_t wide_t = 0xFFFFFFFFu, wide_tri = 0xFFFFFFFFu;  // this lane's best triangle of the shared visit
-        float wide_b1 = 0.0f, wide_b2 = 0.0f;
-        bool wide_external = false;
-        const float visit_near = lr.near_;
-        if (box_hit_packed<RCP>(n0, n1, lr)) {
-            const uint32_t begin = __float_as_uint(n1.z), end = begin + (__float_as_uint(n1.w) & HIPRZ_NODE_COUNT_MASK);
-            for (uint32_t i = begin + j; i < end; i += 8u) {
-                const float4 a = s.tris[3 * i], b = s.tris[3 * i + 1], cc = s.tris[3 * i + 2];
-                float t, b1, b2, det;
-                RZ_PHASE(4);
-                RZ_COUNT(tri_tests);
-                if (tri_hit(xyz(a), xyz(b), xyz(cc), lr, t, b1, b2, det)) {
-                    lr.far_ = t;
-                    wide_t = __float_as_uint(t), wide_tri = i, wide_b1 = b1, wide_b2 = b2, wide_external = det > 0.0f;
-                }
-            }
-        }
-        // the octet's winner hands the visit's hit to the ray's slot (the 8 lanes of a visit take this branch together; distances
-        // are positive: their bits order like they do)
-        const uint32_t t_min = octet_min(wide_t);
-        const bool nearest = wide_t != 0xFFFFFFFFu && wide_t == t_min;
-        const uint32_t first = octet_min(nearest ? wide_tri : 0xFFFFFFFFu);
-        if (nearest && wide_tri == first) {
-            lds.ray[6 * 256 + src] = visit_near / len;
-            lds.ray[7 * 256 + src] = __uint_as_float(wide_t) / len;
-            lds.hit[0 * 256 + src] = wide_tri;
-            lds.hit[1 * 256 + src] = wide_external ? 1u : 0u;
-            lds.hit[2 * 256 + src] = __float_as_uint(wide_b1);
-            lds.hit[3 * 256 + src] = __float_as_uint(wide_b2);
-            lds.hit[4 * 256 + src] = inst;
-        }
-    } else {
-        LdsStack mesh(mesh_column);
-        Hit h;
-        if (closest_in_mesh_stack<COUNT, RCP, false>(s, mesh, x.blas_root, lr, h, cnt)) {  // single-leaf meshes: one box test per visit
-            lds.ray[6 * 256 + src] = lr.near_ / len;
-            lds.ray[7 * 256 + src] = lr.far_ / len;
-            lds.hit[0 * 256 + src] = h.triangle;
-            lds.hit[1 * 256 + src] = h.external ? 1u : 0u;
-            lds.hit[2 * 256 + src] = __float_as_uint(h.bx);
-            lds.hit[3 * 256 + src] = __float_as_uint(h.by);
-            lds.hit[4 * 256 + src] = inst;
-        }
+    LdsStack mesh(mesh_column);
+    Hit h;
+    if (closest_in_mesh_stack<COUNT, RCP, false>(s, mesh, x.blas_root, lr, h, cnt)) {  // the root is an inner node
+        lds.ray[6 * 256 + src] = lr.near_ / len;
+        lds.ray[7 * 256 + src] = lr.far_ / len;
+        lds.hit[0 * 256 + src] = h.triangle;
+        lds.hit[1 * 256 + src] = h.external ? 1u : 0u;
+        lds.hit[2 * 256 + src] = __float_as_uint(h.bx);
+        lds.hit[3 * 256 + src] = __float_as_uint(h.by);
+        lds.hit[4 * 256 + src] = inst;
     }
 }
 
@@ -1500,7 +1248,7 @@ __device__ __forceinline__ int closest_hit_flat(const DScene& s, const FlatWorld
     if (active) {
         RZ_PHASE(0);
         RZ_COUNT(box_tests);
-        if (box_hit_packed<RCP, true>(fw.root0, fw.root1, g)) flat_mask = pretest_leaf_instances<COUNT, RCP>(s, fw, g, tm, true, cnt);
+        if (box_hit_unpacked<RCP>(fw.root0, fw.root1, g)) flat_mask = pretest_leaf_instances<COUNT, RCP>(s, fw, g, tm, true, cnt);
         else root_missed = true;
     }
     // both halves of the double-buffered bins: the round that left the previous call found its own half empty and left the other one,

@@ -132,7 +132,7 @@ struct PackedScene {
     float bounds_min[3] = {0, 0, 0}, bounds_scale[3] = {0, 0, 0};  // the world root's box, 32 cells per axis
     uint32_t tlas_root = 0;
     bool flat_world = false;                  // the world tree is one leaf of at most 8 instances
-    // Pair records: what the one-leaf walk's triangle loop reads (hiprz_device.hpp: binned_visit, RZ_FLAT_PAIR_RECORDS).  NOT part of
+    // Pair records: what the one-leaf walk's triangle loop reads (hiprz_device.hpp: binned_visit).  NOT part of
     // `blob`: the upload places the section directly behind the blob in the device's hot buffer, and DScene::hot_bytes is the total,
     // so whatever stages or sizes the hot buffer carries the section along.  Empty unless the world is flat, the snapshot's own trees
     // are walked and some instance's mesh is ONE leaf.  Layout: a table of ((n_instances + 3) & ~3) 16-bit words — instance id -> where

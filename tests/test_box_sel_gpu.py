@@ -1,14 +1,15 @@
-"""The one-leaf walk's box tests on packed sequences that read the ray by operand select (closest_hit_flat, MODE 4: box_range_sel,
-RZ_FLAT_SEL_BOXES): the root box, the instance boxes tested up front (pretest_leaf_instances, its re-test included) and the visit's mesh
-box, each for a wave of fast rays; a wave with one ray that is not fast takes box_range_unpacked<false> as before.
+"""The one-leaf walk's up-front box tests (closest_hit_flat, MODE 4): the root box, the instance boxes tested before the rounds
+(pretest_leaf_instances, its re-test included) and the visit's mesh box.  pretest_leaf_instances has two loops, and the cases below put
+a world on either side of the choice: a leaf of eight instances under a wave of fast rays takes its eight tests as one straight run
+(box_range_fast, no `k < count`); every other leaf and every wave with one ray that is not fast takes the general loop
+(box_range_unpacked, which itself runs the shared-reciprocal form for a wave of fast rays and true divisions otherwise).
 
-Self-test: ctx.selftest(256, seed) for three seeds.  Its kernel now also compares box_range_sel with box_range_unpacked<true> (tmin and
-tmax bits, on the flat boxes, range ends on a face and nearly parallel rays it draws), called directly whichever way the switch stands;
-the ray's nine values are independent draws and the spare half beside y.z gets a number of its own, so that an operand read from the wrong
-half of a pair shows.  Every mismatch lands in the one counter, which must be zero.
+Self-test: ctx.selftest(256, seed) for three seeds.  Its kernel holds div_shared, which both loops divide with, to the correctly rounded
+quotient bit for bit, the filtered box test to the exact one (flat boxes, range ends on a face, nearly parallel rays), and the triangle
+pair step to the one-by-one loop.  Every mismatch lands in the one counter, which must be zero.
 
 Scenes, by the method of tests/test_packed_pairs_gpu.py: the default traversal on pipelines 2, 0 and 1 against a twin on the LDS-stack
-walk (set_traversal_mode(1): box_hit / div_shared2, which this change leaves alone).  After render(1) and render(3): accumulator,
+walk (set_traversal_mode(1): box_hit / div_shared2, another spelling of the same tests).  After render(1) and render(3): accumulator,
 first-hit depth and path state equal the twin's bit for bit; then render_counted(2): every counter equals the twin's.  One case
 (`flat_and_thick`) is also held to the CPU oracle: segments, hits and finished exact, box and triangle tests net of shadow tests.
 Every frame is 32x8 pixels or smaller.
@@ -32,9 +33,8 @@ Every frame is 32x8 pixels or smaller.
                               re-test path) and to test the visit's mesh box on a rotated, scaled local ray
   not_fast_full_leaf, tiny_origin_full_leaf
                               the two above with the leaf filled to eight instances.  A leaf of eight under a wave of fast rays has its
-                              up-front tests as one straight run (RZ_FLAT_FULL_LEAF; quads_8 and mixed take it in every wave); these two
-                              reach the loop it stands in front of with a full leaf: in every wave, and in the waves that hold a ray
-                              from the camera
+                              up-front tests as one straight run (quads_8 and mixed take it in every wave); these two reach the general
+                              loop behind it with a full leaf: in every wave, and in the waves that hold a ray from the camera
 The tests cannot see which form ran: the library has no counter for it.
 """
 import math

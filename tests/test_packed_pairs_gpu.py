@@ -1,11 +1,10 @@
-"""The packed forms of the one-leaf walk (closest_hit_flat, MODE 4): box tests on register pairs (box_range_packed) and the triangles of a
-leaf tested two at a time (tri_hit2, tri_pair_step, hiprz_pair_pick.hpp).
+"""The packed form of the one-leaf walk (closest_hit_flat, MODE 4): the triangles of a leaf tested two at a time (tri_hit2,
+tri_pair_step, hiprz_pair_pick.hpp), behind box tests that stay one float per lane (box_range_unpacked).
 
-Self-test: ctx.selftest(256, seed) for three seeds.  Its kernel now also compares box_range_packed with box_range_unpacked (tmin and tmax
-bits, on the adversarial boxes it draws) and the pair loop with the one-by-one loop on random and adversarial triangle pairs (identical
-triangles, |det| < 1e-7, an origin in the triangle's plane, t on the near or the far end): far end, winner, b1, b2 and the facing bit.
-Every mismatch lands in the one counter, which must be zero.  (The new comparisons are not added to the kernel's count of cases:
-tests/test_parity_gpu.py bounds that count by what the quotient and filtered-box cases alone give.)
+Self-test: ctx.selftest(256, seed) for three seeds.  Its kernel compares the pair loop with the one-by-one loop on random and
+adversarial triangle pairs (identical triangles, |det| < 1e-7, an origin in the triangle's plane, t on the near or the far end): far end,
+winner, b1, b2 and the facing bit.  Every mismatch lands in the one counter, which must be zero.  (That comparison is not added to the
+kernel's count of cases: tests/test_parity_gpu.py bounds that count by what the quotient and filtered-box cases alone give.)
 
 Scenes, by the method of tests/test_flat_walk_gpu.py: the default traversal on pipelines 2, 0 and 1 against a twin on the LDS-stack walk
 (set_traversal_mode(1)), which tests triangles one by one.  After render(1) and render(3): accumulator, first-hit depth and path state

@@ -1,6 +1,5 @@
-"""The one-leaf walk's triangle loop on pair records (RZ_FLAT_PAIR_RECORDS: the two triangles of a pair stored interleaved behind the hot
-blob, hiprz_scene_host.hpp: PackedScene::pair_section; binned_visit in hiprz_device.hpp) and its two reciprocals as one sequence
-(RZ_FLAT_PK_DIV: rcp_pair).
+"""The one-leaf walk's triangle loop on pair records (the two triangles of a pair stored interleaved behind the hot blob,
+hiprz_scene_host.hpp: PackedScene::pair_section; binned_visit in hiprz_device.hpp).
 
 Every case is a one-leaf world of at most 8 instances whose meshes are single leaves of chosen triangle counts (asserted on the flattened
 scene), rendered 1 + 8 passes through three launch forms — the resident pipeline, the split pipeline, and nine render(1) calls on the
@@ -25,8 +24,8 @@ stack walk's.  Frames are 64 x 48 (12 tiles, more than one workgroup), one is 72
   partial_72x20  3, 12 and 17 triangles on a frame of partial tiles
 
 `counts_small` also goes against the CPU oracle at the project's parity bar (first-hit depth and finished-path counts equal, colours
-within rel 1e-3 on all but 1 % of the pixels), and hiprz_selftest — whose kernel compares rcp_pair with `1.0f / x` bit for bit on random
-bit patterns, nudged determinants, operands at the denormal and overflow ends, zeros, infinities and NaNs — must report no mismatch.
+within rel 1e-3 on all but 1 % of the pixels), and hiprz_selftest — whose kernel compares the step on a pair record's operands
+(tri_pair_step) with the one-by-one loop — must report no mismatch.
 """
 import math
 
