@@ -349,6 +349,7 @@ Engine::~Engine() {
     if (m_query) hiprz_query_destroy(m_query);
     if (m_order) hiprz_order_destroy(m_order);
     if (m_bake) hiprz_bake_destroy(m_bake);
+    if (m_atlas) hiprz_atlas_destroy(m_atlas);
     hiprz_destroy(m_ctx);
 }
 
@@ -441,8 +442,7 @@ std::vector<uint32_t> Engine::occluded(const std::vector<hiprz_ray>& rays, bool 
     return out;
 }
 
-std::vector<hiprz_bake_texel> Engine::bakeOcclusion(const std::vector<hiprz_bake_point>& points, uint32_t K, uint32_t S, uint32_t seed) {
-    std::lock_guard<std::mutex> lock(m_mutex);
+hiprz_bake* Engine::baker(uint32_t K, uint32_t S) {
     if (!m_bake)
         if (const int rc = hiprz_bake_create(&m_bake, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_bake_last_error(nullptr));
     if (K != m_bake_k || S != m_bake_s) {  // the cosine table of (K, S), kept until another is asked for
@@ -451,9 +451,46 @@ std::vector<hiprz_bake_texel> Engine::bakeOcclusion(const std::vector<hiprz_bake
         if (const int rc = hiprz_bake_set_directions(m_bake, table.data(), K, S); rc != HIPRZ_OK) throw Exception(rc, hiprz_bake_last_error(m_bake));
         m_bake_k = K, m_bake_s = S;
     }
+    return m_bake;
+}
+
+std::vector<hiprz_bake_texel> Engine::bakeOcclusion(const std::vector<hiprz_bake_point>& points, uint32_t K, uint32_t S, uint32_t seed) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    baker(K, S);
     std::vector<hiprz_bake_texel> out(points.size());
     if (points.empty()) return out;
     if (const int rc = hiprz_bake_occlusion_host(m_bake, points.data(), points.size(), seed, out.data()); rc != HIPRZ_OK) throw Exception(rc, hiprz_bake_last_error(m_bake));
+    return out;
+}
+
+Engine::BakedAtlas Engine::bakeAtlas(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, uint32_t K, uint32_t S, uint32_t seed, uint32_t rings,
+                                     float near_, float far_) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (parts.empty()) throw Exception(HIPRZ_ERR_INVALID, "bakeAtlas: an atlas needs at least one part");
+    hiprz_bake* b = baker(K, S);
+    if (!m_atlas)
+        if (const int rc = hiprz_atlas_create(&m_atlas, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_atlas_last_error(nullptr));
+    const auto atlas_check = [this](int rc) {
+        if (rc != HIPRZ_OK) throw Exception(rc, hiprz_atlas_last_error(m_atlas));
+    };
+    atlas_check(hiprz_atlas_begin(m_atlas, width, height));
+    size_t base = 0;
+    for (const AtlasPart& part : parts) {  // ids numbered through the list
+        if (base > 0xFFFFFFFFull) throw Exception(HIPRZ_ERR_INVALID, "bakeAtlas: more than 2^32 triangles");
+        atlas_check(hiprz_atlas_add_host(m_atlas, part.charts.data(), part.charts.size(), uint32_t(base), part.instance, near_, far_));
+        base += part.charts.size();
+    }
+    // the points stay on the device: baked into the handle's own records on the context's stream, dilated there, read once
+    const size_t texels = size_t(width) * height;
+    void* records = hiprz_atlas_records_device(m_atlas);
+    if (const int rc = hiprz_bake_occlusion(b, hiprz_atlas_points_device(m_atlas), texels, seed, static_cast<hiprz_bake_texel*>(records), nullptr); rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_bake_last_error(b));
+    atlas_check(hiprz_atlas_dilate(m_atlas, records, rings, nullptr, nullptr));
+    BakedAtlas out;
+    out.width = width, out.height = height;
+    out.texels.resize(texels), out.samples.resize(texels), out.ring.resize(texels);
+    atlas_check(hiprz_atlas_read_records_host(m_atlas, out.texels.data(), out.ring.data()));
+    atlas_check(hiprz_atlas_read_host(m_atlas, nullptr, out.samples.data()));
     return out;
 }
 
@@ -531,6 +568,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_order = nullptr;
                 if (m_bake) hiprz_bake_destroy(m_bake);
                 m_bake = nullptr, m_bake_k = m_bake_s = 0;
+                if (m_atlas) hiprz_atlas_destroy(m_atlas);
+                m_atlas = nullptr;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

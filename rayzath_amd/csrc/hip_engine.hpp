@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "hiprz.h"
+#include "hiprz_atlas.h"
 #include "hiprz_bake.h"
 #include "hiprz_noise.h"
 #include "hiprz_order.h"
@@ -253,6 +254,23 @@ public:
     // the world of the last renderWorld call and the sum of the directions that are not; the rays are made and counted on the device.
     // Waits for the stream; changes no frame.
     std::vector<hiprz_bake_texel> bakeOcclusion(const std::vector<hiprz_bake_point>& points, uint32_t K = 64, uint32_t S = 4, uint32_t seed = 0);
+    // Bake atlases (include/hiprz_atlas.h): the charts of `parts` — triangles with positions and normals in the mesh's own space and UVs in
+    // atlas units, placed as instance `instance` of the world of the last renderWorld call is now, ids numbered through the list — are
+    // rasterised on the device into one surface point per texel of a width x height atlas, the points are baked as bakeOcclusion bakes
+    // them without visiting the host, and the texels are dilated by `rings` rings into the gutters.  Texel (x, y) is entry y * width + x;
+    // ring: 0 covered, r filled in ring r, HIPRZ_ATLAS_NONE still empty.  Waits for the stream; changes no frame.
+    struct AtlasPart {
+        uint32_t instance;
+        std::vector<hiprz_atlas_tri> charts;
+    };
+    struct BakedAtlas {
+        uint32_t width = 0, height = 0;
+        std::vector<hiprz_bake_texel> texels;
+        std::vector<hiprz_atlas_sample> samples;
+        std::vector<uint32_t> ring;
+    };
+    BakedAtlas bakeAtlas(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, uint32_t K = 64, uint32_t S = 4, uint32_t seed = 0, uint32_t rings = 2,
+                         float near_ = 1.0e-3f, float far_ = 3.0e38f);
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -301,6 +319,8 @@ private:
     hiprz_order* order();
     hiprz_bake* m_bake = nullptr;           // bound to m_ctx, created at the first bake; it holds the cosine table of (m_bake_k, m_bake_s)
     uint32_t m_bake_k = 0, m_bake_s = 0;
+    hiprz_bake* baker(uint32_t K, uint32_t S);  // m_bake holding the cosine table of (K, S)
+    hiprz_atlas* m_atlas = nullptr;         // bound to m_ctx, created at the first bakeAtlas
     int wantVariance() const { return m_measuring || (m_denoise && (m_denoise_params.flags & HIPRZ_DENOISE_VARIANCE)) ? 1 : 0; }
     std::mutex m_mutex;  // renderWorld is serialised (cpu_engine_core.cpp:15)
     bool m_pending_readback = false;

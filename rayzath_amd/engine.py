@@ -137,6 +137,9 @@ class Context:
         if getattr(self, "_bake", None) is not None:
             self._bake.close()
             self._bake = None
+        if getattr(self, "_atlas", None) is not None:
+            self._atlas.close()
+            self._atlas = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -490,6 +493,34 @@ class Context:
         """The rays bake_occlusion walks for `points` under the table set before (or `directions`): query.ray_dtype of shape
         points.shape + (K,), to feed to trace / occluded (closest-hit distances for distance-weighted occlusion)."""
         return self._bake_with(directions).rays(points, seed, self.sync)
+
+    # --- bake atlases: UV charts rasterised into surface points on the device, gutters dilated (include/hiprz_atlas.h) ---
+    def atlas(self):
+        """the context's atlas.Atlas, created at the first use (begin, add, add_device, points_device, dilate_device, ...)"""
+        from . import atlas as _atlas
+        if getattr(self, "_atlas", None) is None:
+            self._atlas = _atlas.Atlas(self._ctx)
+        return self._atlas
+
+    def atlas_points(self, parts, width, height, near=1.0e-3, far=3.0e38):
+        """The surface points of a width x height atlas: `parts` is a list of (instance_index, charts) pairs, charts an array of
+        atlas.tri_dtype (atlas.charts(mesh)) in the mesh's own space, placed as the instance is in the context now; triangle ids are
+        numbered through the list.  (points, samples) of shape (height, width): bake.point_dtype and atlas.sample_dtype, a texel no chart
+        covers reads zeros and atlas.NONE.  Waits for the stream; changes no frame."""
+        from . import atlas as _atlas
+        a = self.atlas()
+        _atlas.build(a, parts, width, height, near, far)
+        return a.read()
+
+    def bake_atlas(self, parts, width, height, directions=(64, 4), seed=0, rings=2, near=1.0e-3, far=3.0e38):
+        """atlas_points, bake_occlusion of the points where they lie on the device, and `rings` rings of gutter dilation:
+        (texels, samples, ring) of shape (height, width) — bake.texel_dtype, atlas.sample_dtype and uint32 (0 covered, r filled in ring r,
+        atlas.NONE still empty).  Texel (x, y) is point y * width + x of the bake.  Waits for the stream; changes no frame."""
+        from . import atlas as _atlas
+        a, b = self.atlas(), self._bake_with(directions)
+        _atlas.build(a, parts, width, height, near, far)
+        texels, ring = _atlas.bake(a, b, rings, seed)
+        return texels, a.read(points=False)[1], ring
 
     def pixel_rays(self):
         """(H, W) array of query.ray_dtype: the selected camera's pixel-centre rays, the ones the first pass, the guides and ray_cast walk"""
