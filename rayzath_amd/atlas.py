@@ -153,3 +153,12 @@ def bake(atlas, baker, rings, seed):
     baker.occlusion_device(atlas.points_device(), atlas.width * atlas.height, atlas.records_device(), seed)
     atlas.dilate_device(atlas.records_device(), rings)
     return atlas.read_records(texel_dtype)
+
+
+def bake_light(atlas, lighter, rings, seed, lights=None):
+    """the atlas's points light-baked (light.Light `lighter`) where they lie, into the handle's own records, and those dilated by `rings`
+    rings: (texels, ring) of shape (H, W).  Waits for the context's stream."""
+    from .light import texel_dtype
+    lighter.bake_device(atlas.points_device(), atlas.width * atlas.height, atlas.records_device(), seed, lights)
+    atlas.dilate_device(atlas.records_device(), rings)
+    return atlas.read_records(texel_dtype)

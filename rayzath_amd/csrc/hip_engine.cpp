@@ -350,6 +350,7 @@ Engine::~Engine() {
     if (m_order) hiprz_order_destroy(m_order);
     if (m_bake) hiprz_bake_destroy(m_bake);
     if (m_atlas) hiprz_atlas_destroy(m_atlas);
+    if (m_light) hiprz_light_destroy(m_light);
     hiprz_destroy(m_ctx);
 }
 
@@ -468,6 +469,46 @@ Engine::BakedAtlas Engine::bakeAtlas(const std::vector<AtlasPart>& parts, uint32
     std::lock_guard<std::mutex> lock(m_mutex);
     if (parts.empty()) throw Exception(HIPRZ_ERR_INVALID, "bakeAtlas: an atlas needs at least one part");
     hiprz_bake* b = baker(K, S);
+    atlasWith(parts, width, height, near_, far_, "bakeAtlas");
+    const auto atlas_check = [this](int rc) {
+        if (rc != HIPRZ_OK) throw Exception(rc, hiprz_atlas_last_error(m_atlas));
+    };
+    // the points stay on the device: baked into the handle's own records on the context's stream, dilated there, read once
+    const size_t texels = size_t(width) * height;
+    void* records = hiprz_atlas_records_device(m_atlas);
+    if (const int rc = hiprz_bake_occlusion(b, hiprz_atlas_points_device(m_atlas), texels, seed, static_cast<hiprz_bake_texel*>(records), nullptr); rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_bake_last_error(b));
+    atlas_check(hiprz_atlas_dilate(m_atlas, records, rings, nullptr, nullptr));
+    BakedAtlas out;
+    out.width = width, out.height = height;
+    out.texels.resize(texels), out.samples.resize(texels), out.ring.resize(texels);
+    atlas_check(hiprz_atlas_read_records_host(m_atlas, out.texels.data(), out.ring.data()));
+    atlas_check(hiprz_atlas_read_host(m_atlas, nullptr, out.samples.data()));
+    return out;
+}
+
+hiprz_light* Engine::lighter(uint32_t K, uint32_t S) {
+    if (!m_light)
+        if (const int rc = hiprz_light_create(&m_light, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_light_last_error(nullptr));
+    if (K != m_light_k || S != m_light_s) {  // the disk table of (K, S), kept until another is asked for
+        std::vector<float> table(2 * size_t(K) * S);
+        if (const int rc = hiprz_light_disk_samples(K, S, table.data()); rc != HIPRZ_OK) throw Exception(rc, "bakeLight: K is not a power of two in 1..1024 or S is not in 1..64");
+        if (const int rc = hiprz_light_set_samples(m_light, table.data(), K, S); rc != HIPRZ_OK) throw Exception(rc, hiprz_light_last_error(m_light));
+        m_light_k = K, m_light_s = S;
+    }
+    return m_light;
+}
+
+std::vector<hiprz_light_texel> Engine::bakeLight(const std::vector<hiprz_bake_point>& points, uint32_t K, uint32_t S, uint32_t seed, const hiprz_light_range* range) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    lighter(K, S);
+    std::vector<hiprz_light_texel> out(points.size());
+    if (points.empty()) return out;
+    if (const int rc = hiprz_light_bake_host(m_light, points.data(), points.size(), seed, range, out.data()); rc != HIPRZ_OK) throw Exception(rc, hiprz_light_last_error(m_light));
+    return out;
+}
+
+hiprz_atlas* Engine::atlasWith(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, float near_, float far_, const char* what) {
     if (!m_atlas)
         if (const int rc = hiprz_atlas_create(&m_atlas, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_atlas_last_error(nullptr));
     const auto atlas_check = [this](int rc) {
@@ -476,17 +517,29 @@ Engine::BakedAtlas Engine::bakeAtlas(const std::vector<AtlasPart>& parts, uint32
     atlas_check(hiprz_atlas_begin(m_atlas, width, height));
     size_t base = 0;
     for (const AtlasPart& part : parts) {  // ids numbered through the list
-        if (base > 0xFFFFFFFFull) throw Exception(HIPRZ_ERR_INVALID, "bakeAtlas: more than 2^32 triangles");
+        if (base > 0xFFFFFFFFull) throw Exception(HIPRZ_ERR_INVALID, std::string(what) + ": more than 2^32 triangles");
         atlas_check(hiprz_atlas_add_host(m_atlas, part.charts.data(), part.charts.size(), uint32_t(base), part.instance, near_, far_));
         base += part.charts.size();
     }
+    return m_atlas;
+}
+
+Engine::LitAtlas Engine::bakeLightAtlas(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, uint32_t K, uint32_t S, uint32_t seed, uint32_t rings,
+                                        float near_, float far_, const hiprz_light_range* range) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (parts.empty()) throw Exception(HIPRZ_ERR_INVALID, "bakeLightAtlas: an atlas needs at least one part");
+    hiprz_light* l = lighter(K, S);
+    atlasWith(parts, width, height, near_, far_, "bakeLightAtlas");
+    const auto atlas_check = [this](int rc) {
+        if (rc != HIPRZ_OK) throw Exception(rc, hiprz_atlas_last_error(m_atlas));
+    };
     // the points stay on the device: baked into the handle's own records on the context's stream, dilated there, read once
     const size_t texels = size_t(width) * height;
     void* records = hiprz_atlas_records_device(m_atlas);
-    if (const int rc = hiprz_bake_occlusion(b, hiprz_atlas_points_device(m_atlas), texels, seed, static_cast<hiprz_bake_texel*>(records), nullptr); rc != HIPRZ_OK)
-        throw Exception(rc, hiprz_bake_last_error(b));
+    if (const int rc = hiprz_light_bake(l, hiprz_atlas_points_device(m_atlas), texels, seed, range, static_cast<hiprz_light_texel*>(records), nullptr); rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_light_last_error(l));
     atlas_check(hiprz_atlas_dilate(m_atlas, records, rings, nullptr, nullptr));
-    BakedAtlas out;
+    LitAtlas out;
     out.width = width, out.height = height;
     out.texels.resize(texels), out.samples.resize(texels), out.ring.resize(texels);
     atlas_check(hiprz_atlas_read_records_host(m_atlas, out.texels.data(), out.ring.data()));
@@ -570,6 +623,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_bake = nullptr, m_bake_k = m_bake_s = 0;
                 if (m_atlas) hiprz_atlas_destroy(m_atlas);
                 m_atlas = nullptr;
+                if (m_light) hiprz_light_destroy(m_light);
+                m_light = nullptr, m_light_k = m_light_s = 0;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

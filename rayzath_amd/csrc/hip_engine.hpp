@@ -25,6 +25,7 @@
 #include "hiprz.h"
 #include "hiprz_atlas.h"
 #include "hiprz_bake.h"
+#include "hiprz_light.h"
 #include "hiprz_noise.h"
 #include "hiprz_order.h"
 #include "hiprz_query.h"
@@ -271,6 +272,20 @@ public:
     };
     BakedAtlas bakeAtlas(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, uint32_t K = 64, uint32_t S = 4, uint32_t seed = 0, uint32_t rings = 2,
                          float near_ = 1.0e-3f, float far_ = 3.0e38f);
+    // Light baking (include/hiprz_light.h): per surface point of `points`, the direct light of the spot and direct lights of the world of the
+    // last renderWorld call with their shadows, K shadow rays per light from the disk table (K, S); `range` selects a sub-range of the
+    // lights (nullptr: all of them; one call per range gives per-light maps).  Waits for the stream; changes no frame.
+    std::vector<hiprz_light_texel> bakeLight(const std::vector<hiprz_bake_point>& points, uint32_t K = 16, uint32_t S = 4, uint32_t seed = 0,
+                                             const hiprz_light_range* range = nullptr);
+    // bakeAtlas with bakeLight's quantity per texel: atlas points, the light bake where they lie on the device, `rings` rings of dilation.
+    struct LitAtlas {
+        uint32_t width = 0, height = 0;
+        std::vector<hiprz_light_texel> texels;
+        std::vector<hiprz_atlas_sample> samples;
+        std::vector<uint32_t> ring;
+    };
+    LitAtlas bakeLightAtlas(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, uint32_t K = 16, uint32_t S = 4, uint32_t seed = 0, uint32_t rings = 2,
+                            float near_ = 1.0e-3f, float far_ = 3.0e38f, const hiprz_light_range* range = nullptr);
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -321,6 +336,10 @@ private:
     uint32_t m_bake_k = 0, m_bake_s = 0;
     hiprz_bake* baker(uint32_t K, uint32_t S);  // m_bake holding the cosine table of (K, S)
     hiprz_atlas* m_atlas = nullptr;         // bound to m_ctx, created at the first bakeAtlas
+    hiprz_atlas* atlasWith(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, float near_, float far_, const char* what);  // m_atlas holding the points of `parts` (not empty: the callers refuse that)
+    hiprz_light* m_light = nullptr;         // bound to m_ctx, created at the first light bake; it holds the disk table of (m_light_k, m_light_s)
+    uint32_t m_light_k = 0, m_light_s = 0;
+    hiprz_light* lighter(uint32_t K, uint32_t S);  // m_light holding the disk table of (K, S)
     int wantVariance() const { return m_measuring || (m_denoise && (m_denoise_params.flags & HIPRZ_DENOISE_VARIANCE)) ? 1 : 0; }
     std::mutex m_mutex;  // renderWorld is serialised (cpu_engine_core.cpp:15)
     bool m_pending_readback = false;

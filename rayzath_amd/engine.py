@@ -140,6 +140,9 @@ class Context:
         if getattr(self, "_atlas", None) is not None:
             self._atlas.close()
             self._atlas = None
+        if getattr(self, "_light", None) is not None:
+            self._light.close()
+            self._light = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -520,6 +523,45 @@ class Context:
         a, b = self.atlas(), self._bake_with(directions)
         _atlas.build(a, parts, width, height, near, far)
         texels, ring = _atlas.bake(a, b, rings, seed)
+        return texels, a.read(points=False)[1], ring
+
+    # --- light baking: the shadowed direct light of the scene's own lights per surface point (include/hiprz_light.h) ---
+    def light(self):
+        """the context's light.Light, created at the first use (device-pointer calls: bake_device, rays_device)"""
+        from . import light as _light
+        if getattr(self, "_light", None) is None:
+            self._light = _light.Light(self._ctx)
+        return self._light
+
+    def _light_with(self, samples):
+        h = self.light()
+        if samples is not None and not (isinstance(samples, tuple) and samples == h.table):       # a disk table already set is not set again
+            h.set_samples(samples)
+        return h
+
+    def bake_light(self, points, samples=(16, 4), seed=0, lights=None):
+        """The direct light of the uploaded scene's spot and direct lights at every surface point of `points` (an array of
+        bake.point_dtype), with their shadows: an array of light.texel_dtype of the same shape — `light` is the RGB irradiance-like sum
+        include/hiprz_light.h defines (multiply by the surface colour), `shadowed` the number of shadow rays found occluded
+        (light.INVALID for an invalid point).  samples: a (K, S) pair for the library's disk table of S sets of K samples (K = 1: hard
+        shadows), an (S, K, 2) float32 array of points of the unit disk, or None for the table set before.  lights: None for every light
+        or (spot_first, spot_count, direct_first, direct_count), a count of None meaning "to the end" — one call per range gives
+        per-light maps.  Waits for the stream; changes no frame."""
+        return self._light_with(samples).bake(points, seed, lights)
+
+    def light_rays(self, points, seed=0, samples=None, lights=None):
+        """(rays, weights): the shadow rays bake_light walks for `points` under the table set before (or `samples`) and their weights —
+        query.ray_dtype and float32 of shape points.shape + (L, K), spot lights first; a skipped sample reads direction 0 and weight 0."""
+        return self._light_with(samples).rays(points, seed, lights, self.sync)
+
+    def bake_light_atlas(self, parts, width, height, samples=(16, 4), seed=0, rings=2, near=1.0e-3, far=3.0e38, lights=None):
+        """atlas_points, bake_light of the points where they lie on the device, and `rings` rings of gutter dilation: (texels, samples,
+        ring) of shape (height, width) — light.texel_dtype, atlas.sample_dtype and uint32 (0 covered, r filled in ring r, atlas.NONE still
+        empty).  Texel (x, y) is point y * width + x of the bake.  Waits for the stream; changes no frame."""
+        from . import atlas as _atlas
+        a, h = self.atlas(), self._light_with(samples)
+        _atlas.build(a, parts, width, height, near, far)
+        texels, ring = _atlas.bake_light(a, h, rings, seed, lights)
         return texels, a.read(points=False)[1], ring
 
     def pixel_rays(self):
