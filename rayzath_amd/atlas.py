@@ -162,3 +162,45 @@ def bake_light(atlas, lighter, rings, seed, lights=None):
     lighter.bake_device(atlas.points_device(), atlas.width * atlas.height, atlas.records_device(), seed, lights)
     atlas.dilate_device(atlas.records_device(), rings)
     return atlas.read_records(texel_dtype)
+
+
+def bake_bounce(atlas, lighter, gatherer, albedo, emission, bounces, rings, seed, lights, sky, sync):
+    """the atlas's points light-baked (light.Light `lighter`) and then, `bounces` times: the source albedo * (direct + indirect) + emission
+    composed per texel, dilated by `rings` rings and gathered (gather.Gather `gatherer`, its chart map set for this atlas) back at the
+    points.  Points, sources and texels stay on the device; albedo and emission are (H, W) arrays of 16-byte records (emission may be
+    None).  (direct, indirect, ring) of shape (H, W), both dilated: light.texel_dtype, gather.texel_dtype and the ring map.  `sync` waits
+    for the context's stream."""
+    from . import _hiprt
+    from .gather import texel_dtype as gathered_dtype
+    from .light import texel_dtype as light_dtype
+    if bounces < 1:
+        raise ValueError("a bounce bake takes at least one bounce")
+    shape, n = (atlas.height, atlas.width), atlas.width * atlas.height
+    for a in (albedo, emission):
+        if a is not None and (a.dtype.itemsize != 16 or a.shape != shape):
+            raise TypeError("albedo and emission must be (H, W) arrays of 16-byte records")
+    sync()
+    bufs = []
+    try:
+        direct, indirect, source, ring = (_hiprt.DeviceBuffer(n * size) for size in (16, 16, 16, 4))
+        bufs += [direct, indirect, source, ring]
+        d_albedo = _hiprt.DeviceBuffer.of(albedo)
+        bufs.append(d_albedo)
+        d_emission = None if emission is None else _hiprt.DeviceBuffer.of(emission)
+        bufs.append(d_emission)
+        points = atlas.points_device()
+        lighter.bake_device(points, n, direct.ptr, seed, lights)
+        gathered = None
+        for _ in range(bounces):
+            gatherer.compose_device(direct.ptr, gathered, d_albedo.ptr, None if d_emission is None else d_emission.ptr, source.ptr, n)
+            atlas.dilate_device(source.ptr, rings)
+            gatherer.texels_device(points, n, source.ptr, atlas.width, atlas.height, indirect.ptr, seed, sky)
+            gathered = indirect.ptr
+        atlas.dilate_device(direct.ptr, rings)
+        atlas.dilate_device(indirect.ptr, rings, ring.ptr)
+        sync()
+        return direct.download(shape, light_dtype), indirect.download(shape, gathered_dtype), ring.download(shape, np.uint32)
+    finally:
+        for b in bufs:
+            if b is not None:
+                b.free()

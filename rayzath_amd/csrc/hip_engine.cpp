@@ -351,6 +351,7 @@ Engine::~Engine() {
     if (m_bake) hiprz_bake_destroy(m_bake);
     if (m_atlas) hiprz_atlas_destroy(m_atlas);
     if (m_light) hiprz_light_destroy(m_light);
+    if (m_gather) hiprz_gather_destroy(m_gather);
     hiprz_destroy(m_ctx);
 }
 
@@ -547,6 +548,81 @@ Engine::LitAtlas Engine::bakeLightAtlas(const std::vector<AtlasPart>& parts, uin
     return out;
 }
 
+Engine::ChartMap Engine::chartMap(const std::vector<AtlasPart>& parts, uint32_t n_instances) {
+    ChartMap map;
+    map.base.assign(n_instances, HIPRZ_GATHER_NONE);
+    for (const AtlasPart& part : parts) {  // ids numbered through the list, as atlasWith numbers them
+        if (part.instance >= n_instances) throw Exception(HIPRZ_ERR_INVALID, "chartMap: a part names an instance the world does not have");
+        if (map.base[part.instance] != HIPRZ_GATHER_NONE) throw Exception(HIPRZ_ERR_INVALID, "chartMap: an instance is in two parts");
+        if (map.uv.size() + part.charts.size() > HIPRZ_GATHER_MAX_CHARTS) throw Exception(HIPRZ_ERR_INVALID, "chartMap: more charts than there are ids");
+        map.base[part.instance] = uint32_t(map.uv.size());
+        for (const hiprz_atlas_tri& t : part.charts) map.uv.push_back(hiprz_gather_chart{t.u1, t.v1, t.u2, t.v2, t.u3, t.v3, {0.0f, 0.0f}});
+    }
+    return map;
+}
+
+hiprz_gather* Engine::gatherer(uint32_t K, uint32_t S, const ChartMap& charts) {
+    if (!m_gather)
+        if (const int rc = hiprz_gather_create(&m_gather, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_gather_last_error(nullptr));
+    if (K != m_gather_k || S != m_gather_s) {  // the cosine table of (K, S), kept until another is asked for
+        std::vector<float> table(4 * size_t(K) * S);
+        if (const int rc = hiprz_bake_cosine_directions(K, S, table.data()); rc != HIPRZ_OK) throw Exception(rc, "gather: K is not one of 16 .. 1024 (powers of two) or S is not in 1..64");
+        if (const int rc = hiprz_gather_set_directions(m_gather, table.data(), K, S); rc != HIPRZ_OK) throw Exception(rc, hiprz_gather_last_error(m_gather));
+        m_gather_k = K, m_gather_s = S;
+    }
+    if (const int rc = hiprz_gather_set_charts(m_gather, charts.base.data(), uint32_t(charts.base.size()), charts.uv.data(), uint32_t(charts.uv.size())); rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_gather_last_error(m_gather));
+    return m_gather;
+}
+
+std::vector<hiprz_gather_texel> Engine::gather(const std::vector<hiprz_bake_point>& points, const std::vector<Record>& source, uint32_t width, uint32_t height,
+                                               const ChartMap& charts, uint32_t K, uint32_t S, uint32_t seed, const float* sky) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (source.size() != size_t(width) * height) throw Exception(HIPRZ_ERR_INVALID, "gather: the source is not width x height records");
+    hiprz_gather* g = gatherer(K, S, charts);
+    std::vector<hiprz_gather_texel> out(points.size());
+    if (points.empty()) return out;
+    const float black[3] = {0.0f, 0.0f, 0.0f};
+    if (const int rc = hiprz_gather_texels_host(g, points.data(), points.size(), seed, source.data(), width, height, sky ? sky : black, out.data()); rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_gather_last_error(g));
+    return out;
+}
+
+Engine::BouncedAtlas Engine::bakeBounceAtlas(const std::vector<AtlasPart>& parts, uint32_t n_instances, uint32_t width, uint32_t height, const std::vector<Record>& albedo,
+                                             const std::vector<Record>& emission, uint32_t bounces, uint32_t K, uint32_t S, uint32_t light_K, uint32_t light_S, uint32_t seed,
+                                             uint32_t rings, const float* sky, float near_, float far_) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    const size_t texels = size_t(width) * height;
+    if (parts.empty()) throw Exception(HIPRZ_ERR_INVALID, "bakeBounceAtlas: an atlas needs at least one part");
+    if (bounces < 1u) throw Exception(HIPRZ_ERR_INVALID, "bakeBounceAtlas: a bounce bake takes at least one bounce");
+    if (albedo.size() != texels || (!emission.empty() && emission.size() != texels)) throw Exception(HIPRZ_ERR_INVALID, "bakeBounceAtlas: albedo and emission are width x height records");
+    hiprz_light* l = lighter(light_K, light_S);
+    hiprz_gather* g = gatherer(K, S, chartMap(parts, n_instances));
+    atlasWith(parts, width, height, near_, far_, "bakeBounceAtlas");
+    const auto atlas_check = [this](int rc) {
+        if (rc != HIPRZ_OK) throw Exception(rc, hiprz_atlas_last_error(m_atlas));
+    };
+    const auto gather_check = [g](int rc) {
+        if (rc != HIPRZ_OK) throw Exception(rc, hiprz_gather_last_error(g));
+    };
+    std::vector<hiprz_bake_point> points(texels);
+    atlas_check(hiprz_atlas_read_host(m_atlas, points.data(), nullptr));
+    BouncedAtlas out;
+    out.width = width, out.height = height;
+    out.direct.resize(texels), out.indirect.resize(texels), out.ring.resize(texels);
+    if (const int rc = hiprz_light_bake_host(l, points.data(), texels, seed, nullptr, out.direct.data()); rc != HIPRZ_OK) throw Exception(rc, hiprz_light_last_error(l));
+    const float black[3] = {0.0f, 0.0f, 0.0f};
+    std::vector<Record> source(texels);
+    for (uint32_t b = 0; b < bounces; ++b) {
+        gather_check(hiprz_gather_compose_host(g, out.direct.data(), b ? out.indirect.data() : nullptr, albedo.data(), emission.empty() ? nullptr : emission.data(), source.data(), texels));
+        atlas_check(hiprz_atlas_dilate_host(m_atlas, source.data(), rings, nullptr));
+        gather_check(hiprz_gather_texels_host(g, points.data(), texels, seed, source.data(), width, height, sky ? sky : black, out.indirect.data()));
+    }
+    atlas_check(hiprz_atlas_dilate_host(m_atlas, out.direct.data(), rings, nullptr));
+    atlas_check(hiprz_atlas_dilate_host(m_atlas, out.indirect.data(), rings, out.ring.data()));
+    return out;
+}
+
 Engine::NoiseResult Engine::renderUntil(World& world, const RenderConfig& cfg, float target, uint32_t max_passes, uint32_t min_batches) {
     if (max_passes < 1u || min_batches < 2u) throw Exception(HIPRZ_ERR_INVALID, "renderUntil: max_passes must be at least 1 and min_batches at least 2");
     setMeasuring(true);
@@ -625,6 +701,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_atlas = nullptr;
                 if (m_light) hiprz_light_destroy(m_light);
                 m_light = nullptr, m_light_k = m_light_s = 0;
+                if (m_gather) hiprz_gather_destroy(m_gather);
+                m_gather = nullptr, m_gather_k = m_gather_s = 0;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

@@ -25,6 +25,7 @@
 #include "hiprz.h"
 #include "hiprz_atlas.h"
 #include "hiprz_bake.h"
+#include "hiprz_gather.h"
 #include "hiprz_light.h"
 #include "hiprz_noise.h"
 #include "hiprz_order.h"
@@ -286,6 +287,35 @@ public:
     };
     LitAtlas bakeLightAtlas(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, uint32_t K = 16, uint32_t S = 4, uint32_t seed = 0, uint32_t rings = 2,
                             float near_ = 1.0e-3f, float far_ = 3.0e38f, const hiprz_light_range* range = nullptr);
+    // Bounce baking (include/hiprz_gather.h): per surface point of `points`, the mean over the K hemisphere rays of the cosine table (K, S) of
+    // what the width x height atlas `source` (16-byte records: RGB and a word, HIPRZ_GATHER_INVALID where a texel has no value) holds under
+    // each ray's closest hit in the world of the last renderWorld call; `sky` (three floats, nullptr: 0) for a ray that hits nothing.  The
+    // chart map says where a hit lies in the atlas: chartMap(parts, n) for the parts of an atlas over a world of n instances.  Waits for the
+    // stream; changes no frame.
+    struct Record {  // a source, albedo or emission texel
+        float rgb[3];
+        uint32_t word;
+    };
+    struct ChartMap {
+        std::vector<uint32_t> base;  // per instance: the id of its first chart, HIPRZ_GATHER_NONE for one that is in no part
+        std::vector<hiprz_gather_chart> uv;
+    };
+    static ChartMap chartMap(const std::vector<AtlasPart>& parts, uint32_t n_instances);
+    std::vector<hiprz_gather_texel> gather(const std::vector<hiprz_bake_point>& points, const std::vector<Record>& source, uint32_t width, uint32_t height,
+                                           const ChartMap& charts, uint32_t K = 64, uint32_t S = 4, uint32_t seed = 0, const float* sky = nullptr);
+    // bakeLightAtlas and then `bounces` radiosity steps: the source albedo * (direct + indirect) + emission per texel (emission may be
+    // empty: 0), `rings` rings of dilation, and the gather at the atlas's points.  `direct` and `indirect` come back dilated, with the ring
+    // map of bakeLightAtlas.  This host has no device allocator of its own: the steps go through the libraries' host-pointer calls, and
+    // give the bytes of Context.bake_bounce_atlas, which keeps everything on the device.
+    struct BouncedAtlas {
+        uint32_t width = 0, height = 0;
+        std::vector<hiprz_light_texel> direct;
+        std::vector<hiprz_gather_texel> indirect;
+        std::vector<uint32_t> ring;
+    };
+    BouncedAtlas bakeBounceAtlas(const std::vector<AtlasPart>& parts, uint32_t n_instances, uint32_t width, uint32_t height, const std::vector<Record>& albedo,
+                                 const std::vector<Record>& emission, uint32_t bounces = 1, uint32_t K = 64, uint32_t S = 4, uint32_t light_K = 16, uint32_t light_S = 4,
+                                 uint32_t seed = 0, uint32_t rings = 2, const float* sky = nullptr, float near_ = 1.0e-3f, float far_ = 3.0e38f);
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -340,6 +370,9 @@ private:
     hiprz_light* m_light = nullptr;         // bound to m_ctx, created at the first light bake; it holds the disk table of (m_light_k, m_light_s)
     uint32_t m_light_k = 0, m_light_s = 0;
     hiprz_light* lighter(uint32_t K, uint32_t S);  // m_light holding the disk table of (K, S)
+    hiprz_gather* m_gather = nullptr;       // bound to m_ctx, created at the first gather; it holds the cosine table of (m_gather_k, m_gather_s)
+    uint32_t m_gather_k = 0, m_gather_s = 0;
+    hiprz_gather* gatherer(uint32_t K, uint32_t S, const ChartMap& charts);  // m_gather holding the cosine table of (K, S) and `charts`
     int wantVariance() const { return m_measuring || (m_denoise && (m_denoise_params.flags & HIPRZ_DENOISE_VARIANCE)) ? 1 : 0; }
     std::mutex m_mutex;  // renderWorld is serialised (cpu_engine_core.cpp:15)
     bool m_pending_readback = false;

@@ -143,6 +143,9 @@ class Context:
         if getattr(self, "_light", None) is not None:
             self._light.close()
             self._light = None
+        if getattr(self, "_gather", None) is not None:
+            self._gather.close()
+            self._gather = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -161,6 +164,7 @@ class Context:
     def upload_scene(self, flat_scene):
         self._check(self.lib.hiprz_upload_scene(self._ctx, C.byref(flat_scene.struct)))
         self._uploaded_map_ids = getattr(flat_scene, "map_ids", None)
+        self._n_instances = int(flat_scene.struct.n_instances)      # (update_instances takes all of them: the number stays)
 
     def upload_camera(self, camera_struct_):
         self._check(self.lib.hiprz_upload_camera(self._ctx, C.byref(camera_struct_)))
@@ -563,6 +567,56 @@ class Context:
         _atlas.build(a, parts, width, height, near, far)
         texels, ring = _atlas.bake_light(a, h, rings, seed, lights)
         return texels, a.read(points=False)[1], ring
+
+    # --- bounce baking: the light an atlas holds, gathered over the hemisphere of a surface point (include/hiprz_gather.h) ---
+    def gatherer(self):
+        """the context's gather.Gather, created at the first use (device-pointer calls: texels_device, samples_device, compose_device)"""
+        from . import gather as _gather
+        if getattr(self, "_gather", None) is None:
+            self._gather = _gather.Gather(self._ctx)
+        return self._gather
+
+    def _gather_with(self, directions, charts):
+        g = self.gatherer()
+        if directions is not None and not (isinstance(directions, tuple) and directions == g.table):       # a cosine table already set is not set again
+            g.set_directions(directions)
+        if charts is not None:
+            g.set_charts(*charts)
+        return g
+
+    def gather(self, points, source, width, height, charts, directions=(64, 4), seed=0, sky=(0.0, 0.0, 0.0)):
+        """The light that reaches every surface point of `points` (an array of bake.point_dtype) after one bounce: the mean over the K
+        hemisphere rays of the point (the rays of bake_rays for the same table and seed) of what the width x height atlas `source` —
+        16-byte records, RGB and a word that is gather.INVALID where a texel has no value — holds under each ray's closest hit, `sky` for
+        a ray that hits nothing, 0 for a back face, an instance outside the atlas or a texel without a value.  charts: (base, uv) of
+        gather.chart_tables(parts, n_instances), or None for the map set before.  An array of gather.texel_dtype of the same shape:
+        `mean`, and `counts` = rays that read a texel | rays that missed << 16 (gather.INVALID for an invalid point).  Waits for the
+        stream; changes no frame."""
+        return self._gather_with(directions, charts).texels(points, source, width, height, seed, sky)
+
+    def gather_samples(self, points, seed=0, directions=None, charts=None):
+        """What gather walks for `points` under the table and the chart map set before (or `directions`, `charts`): gather.sample_dtype of
+        shape points.shape + (K,) — the chart id under the closest hit of ray k or one of gather.MISS / UNMAPPED / BACK / INVALID_RAY,
+        the hit's barycentric weights of vertices 2 and 3, and its distance."""
+        return self._gather_with(directions, charts).samples(points, seed, self.sync)
+
+    def bake_bounce_atlas(self, parts, width, height, albedo, emission=None, bounces=1, directions=(64, 4), samples=(16, 4), seed=0, rings=2, sky=(0.0, 0.0, 0.0),
+                          near=1.0e-3, far=3.0e38, lights=None):
+        """atlas_points, bake_light of the points and then `bounces` radiosity steps on the device: the source albedo * (direct + indirect)
+        + emission per texel, `rings` rings of gutter dilation, and gather at the points.  albedo and emission: a colour (3,), an
+        (height, width, 3) array or (height, width) 16-byte records; emission None is 0.  (direct, indirect, ring) of shape (height,
+        width), both dilated — light.texel_dtype, gather.texel_dtype and the ring map of bake_light_atlas; albedo * (direct.light +
+        indirect.mean) + emission is what a texel sends on.  Points, sources and texels never visit the host between the steps.  Waits for
+        the stream; changes no frame."""
+        from . import atlas as _atlas
+        from . import gather as _gather
+        shape = (height, width)
+        albedo = _gather.records(albedo, shape)
+        emission = None if emission is None else _gather.records(emission, shape)
+        a, h = self.atlas(), self._light_with(samples)
+        _atlas.build(a, parts, width, height, near, far)
+        g = self._gather_with(directions, _gather.chart_tables(parts, getattr(self, "_n_instances", 0)))
+        return _atlas.bake_bounce(a, h, g, albedo, emission, bounces, rings, seed, lights, sky, self.sync)
 
     def pixel_rays(self):
         """(H, W) array of query.ray_dtype: the selected camera's pixel-centre rays, the ones the first pass, the guides and ray_cast walk"""
