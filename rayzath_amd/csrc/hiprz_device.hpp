@@ -18,6 +18,7 @@
 
 #define RZ_DEV __device__ __forceinline__
 #include "hiprz_flat_pick.hpp"
+#include "hiprz_deal_pick.hpp"
 #include "hiprz_pair_pick.hpp"
 #include "hiprz_u8_div.hpp"
 
@@ -918,6 +919,158 @@ RZ_DEV uint32_t pretest_leaf_instances(const DScene& s, const FlatWorld& fw, con
 // C of a binned round for closest_hit_flat: the lane that holds dense item `slot` enters the item's instance for the item's ray.
 // closest_hit_binned keeps its own copy of these lines in place: called from here its code came out of the compiler in another
 // order, and the general walk's kernels are to stay the instructions they were.
+// Lane crossings of the dealing: both go through the LDS crossbar and take no LDS bytes.  All 64 lanes must be active.
+RZ_DEV uint32_t lane_pull(uint32_t from_lane, uint32_t v) { return uint32_t(__builtin_amdgcn_ds_bpermute(int(from_lane << 2), int(v))); }
+RZ_DEV float lane_pull(uint32_t from_lane, float v) { return __uint_as_float(lane_pull(from_lane, __float_as_uint(v))); }
+template <int N>
+RZ_DEV uint32_t row_below(uint32_t v) {  // v of the lane N below within the row of 16, 0 where there is none (row_shr:N, bound_ctrl)
+    return uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x110 + N, 0xF, 0xF, true));
+}
+RZ_DEV uint32_t wave_inclusive_sum(uint32_t v, uint32_t lane) {
+    v += row_below<1>(v), v += row_below<2>(v), v += row_below<4>(v), v += row_below<8>(v);
+    const uint32_t r0 = uint32_t(__builtin_amdgcn_readlane(int(v), 15)), r1 = uint32_t(__builtin_amdgcn_readlane(int(v), 31));
+    const uint32_t r2 = uint32_t(__builtin_amdgcn_readlane(int(v), 47));
+    return v + (lane >= 16u ? r0 : 0u) + (lane >= 32u ? r1 : 0u) + (lane >= 48u ? r2 : 0u);
+}
+// C of a round of closest_hit_flat that has one lane per visit, for a wave that holds a few visits of long leaves: the later pairs of
+// those leaves are dealt over the wave's lanes.  Entered by the WHOLE wave (has_item: this lane holds item `slot`); the lanes without an
+// item are there to be dealt work.  Every lane with an item does what binned_visit does up to and including its first pair: ray from
+// the LDS slot, instance entry, the mesh root's box, pair 0.  It then has `rem` pairs left, T in the wave.  Where deal_taken
+// (hiprz_deal_pick.hpp) declines — T above one trip of 64, or no visit with three pairs left — every lane walks on by itself, the same
+// loop.  Otherwise what pair 0 hit goes to the ray's slot at once, the pairs left become work items 0 .. T - 1 in lane order, item w for
+// lane w, and the lane finds its owner by a search over the prefix sums of rem, pulls the owner's local ray, its far end after pair 0,
+// its record base and its leaf's range (ds_bpermute_b32: the LDS crossbar, no LDS bytes) and takes ONE more trip of the loop.  Each
+// owner then reads its helpers' distances in pair order, keeps the first that is strictly nearest (deal_nearer), pulls that hit's three
+// other words and writes the slot over.  The merge is exact for octet_min's reason: tri_pair_step has no early exit, every pair is
+// tested exactly once against a range that contains the visit's final one, a helper's accepted distance is strictly below pair 0's, and
+// among equal distances the first in leaf order is kept: what the lone loop ends with.  tri_tests grows in the lane that tests the
+// pair, box_tests once per visit in its owner: the sums are the same.  This is a second copy of the entry and of the pair step beside
+// binned_visit's: as ONE function for every wave (idle lanes initialised, the loop on a wave vote) the common path grew by some 40
+// instructions per visit and config B lost 3 % before the dealing gave 2 % back (profiles/r28).
+RZ_DEV void dealt_hit(const BinnedLds& lds, uint32_t item, float near_, float len, const LeafBest& best) {
+    const uint32_t inst = item >> 8, src = item & 255u;
+    lds.ray[6 * 256 + src] = near_ / len;
+    lds.ray[7 * 256 + src] = best.far_ / len;
+    lds.hit[0 * 256 + src] = best.triangle;
+    lds.hit[1 * 256 + src] = best.external ? 1u : 0u;
+    lds.hit[2 * 256 + src] = __float_as_uint(best.b1);
+    lds.hit[3 * 256 + src] = __float_as_uint(best.b2);
+    lds.hit[4 * 256 + src] = inst;
+}
+// Returns true in the lanes whose mesh root is an inner node: their visit is left to binned_visit.
+template <bool COUNT, bool RCP>
+RZ_DEV bool dealt_visit(const DScene& s, const BinnedLds& lds, bool scene_fast, uint32_t slot, bool has_item, Counters& cnt) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned char* section = pair_section(s);
+    uint32_t item = 0u, rec_off = 0u, begin = 0u, count = 0u, n_pairs = 0u, p = 0u;
+    WalkRay lr;
+    lr.o = lr.d = lr.y = V3(0.0f, 0.0f, 0.0f), lr.near_ = lr.far_ = 0.0f, lr.fast = false;
+    float len = 1.0f;
+    bool inner = false;
+    if (has_item) {
+        item = lds.items[slot];
+        const uint32_t inst = item >> 8, src = item & 255u;  // (a round on one lane per visit: no item carries RZ_BIN_WIDE)
+        WalkRay w;
+        w.o = V3(lds.ray[0 * 256 + src], lds.ray[1 * 256 + src], lds.ray[2 * 256 + src]);
+        w.d = V3(lds.ray[3 * 256 + src], lds.ray[4 * 256 + src], lds.ray[5 * 256 + src]);
+        w.near_ = lds.ray[6 * 256 + src], w.far_ = lds.ray[7 * 256 + src];
+        const InstanceXform x = load_instance_xform(s, inst);
+        const float4 n0 = s.nodes[2 * x.blas_root], n1 = s.nodes[2 * x.blas_root + 1];
+        inner = (__float_as_uint(n1.w) & HIPRZ_NODE_LEAF) == 0u;
+        if (!inner) {  // a mesh that is one leaf: pairs 0, 1, ... — or 0 and what the lane is dealt
+            RZ_PHASE(2);
+            len = to_local<RCP>(x, w, lr, scene_fast);
+            RZ_PHASE(3);
+            RZ_COUNT(box_tests);
+            if (box_hit_unpacked<RCP>(n0, n1, lr)) {
+                begin = __float_as_uint(n1.z), count = __float_as_uint(n1.w) & HIPRZ_NODE_COUNT_MASK, n_pairs = (count + 1u) >> 1;
+                rec_off = 8u * reinterpret_cast<const uint16_t*>(section)[inst];
+            }
+        }
+    }
+    LeafBest best;
+    best.far_ = lr.far_, best.triangle = 0xFFFFFFFFu, best.b1 = best.b2 = 0.0f, best.external = false;
+    bool work = p < n_pairs;
+    bool first = true, dealt = false;  // (wave-uniform)
+    // what an owner keeps of its own visit while its registers hold the work it was dealt
+    float own_near = 0.0f;
+    uint32_t rem = 0u, excl = 0u;
+#pragma clang loop unroll(disable)  // (peeled into three copies of the pair step it lost 0.4 %, profiles/r28)
+    while (__any(work)) {  // at most max(n_pairs) trips
+        if (work) {
+            // Pair record p of the leaf holds its triangles 2p and 2p + 1, interleaved: one address, nine 8-byte values in five reads, and
+            // the registers are tri_hit2's operands as they arrive.  The b half of an odd leaf's last record repeats a and is masked by has_b.
+            const float2* q = reinterpret_cast<const float2*>(section + rec_off) + p * (RZ_PAIR_RECORD_BYTES / 8u);
+            const float2 v1x = q[0], v1y = q[1], v1z = q[2], e1x = q[3], e1y = q[4], e1z = q[5], e2x = q[6], e2y = q[7], e2z = q[8];
+            const bool has_b = 2u * p + 1u < count;
+            const uint32_t i = begin + 2u * p;
+            RZ_PHASE(4);
+#ifdef RZ_PHASE_STATS
+            if (p >= 1u) { RZ_PHASE(9); }
+            if (dealt) { RZ_PHASE(14); }
+#endif
+            if constexpr (COUNT) cnt.tri_tests += has_b ? 2u : 1u;
+            tri_pair_step(v3p{f2{v1x.x, v1x.y}, f2{v1y.x, v1y.y}, f2{v1z.x, v1z.y}}, v3p{f2{e1x.x, e1x.y}, f2{e1y.x, e1y.y}, f2{e1z.x, e1z.y}},
+                          v3p{f2{e2x.x, e2x.y}, f2{e2y.x, e2y.y}, f2{e2z.x, e2z.y}}, i, has_b, lr, best);
+        }
+        if (dealt) break;  // one dealt trip (kDealMaxChunks)
+        p += 1u, work = p < n_pairs;
+        if (first) {  // behind every owner's pair 0: deal what is left?
+            first = false;
+            rem = work ? n_pairs - p : 0u;
+#ifdef RZ_PHASE_STATS
+            if (rem != 0u) {
+                const uint32_t k = uint32_t(__popcll(__ballot(1)));
+                RZ_PHASE(10);
+                if (k <= 12u) { RZ_PHASE(11); } else if (k <= 25u) { RZ_PHASE(12); } else { RZ_PHASE(13); }
+            }
+#endif
+            if (__any(rem >= kDealMinRem)) {
+                const uint32_t incl = wave_inclusive_sum(rem, lane);
+                const uint32_t total = uint32_t(__builtin_amdgcn_readlane(int(incl), 63));
+                if (deal_taken(total, kDealMinRem)) {  // (some owner has kDealMinRem left: with one trip the rule asks no more of max_rem)
+                    dealt = true;
+                    excl = incl - rem;
+                    // what pair 0 hit (and a finished visit's hit) goes to the ray's slot now: a helper's hit is strictly nearer and
+                    // overwrites it, and the owner need not keep it
+                    if (best.triangle != 0xFFFFFFFFu) dealt_hit(lds, item, lr.near_, len, best);
+                    own_near = lr.near_;
+                    const uint32_t owner = deal_owner(lane, [&](uint32_t k) { return lane_pull(k, incl); });
+                    p = deal_pair(lane, lane_pull(owner, excl));
+                    lr.o = V3(lane_pull(owner, lr.o.x), lane_pull(owner, lr.o.y), lane_pull(owner, lr.o.z));
+                    lr.d = V3(lane_pull(owner, lr.d.x), lane_pull(owner, lr.d.y), lane_pull(owner, lr.d.z));
+                    lr.near_ = lane_pull(owner, lr.near_);
+                    best.far_ = lane_pull(owner, best.far_);  // the owner's far end after its pair 0
+                    best.triangle = 0xFFFFFFFFu, best.b1 = best.b2 = 0.0f, best.external = false;
+                    rec_off = lane_pull(owner, rec_off), begin = lane_pull(owner, begin), count = lane_pull(owner, count);
+                    work = lane < total;
+                }
+            }
+        }
+    }
+    if (dealt) {
+        // a result is four words: distance (kDealNoHit: the pair was missed), triangle with the facing bit on top, b1, b2
+        const uint32_t res_t = best.triangle != 0xFFFFFFFFu ? __float_as_uint(best.far_) : kDealNoHit;
+        const uint32_t res_triangle = best.triangle | (best.external ? kDealExternal : 0u);
+        const float res_b1 = best.b1, res_b2 = best.b2;
+        uint32_t nearest = kDealNoHit, from = kDealNoHit;
+        for (uint32_t q = 0u; __any(q < rem); ++q) {  // the owner's helpers are lanes excl .. excl + rem - 1, in pair order
+            const uint32_t t = lane_pull(excl + q, res_t);
+            if (q < rem && deal_nearer(t, nearest)) nearest = t, from = excl + q;
+        }
+        const bool won = from != kDealNoHit;  // a helper's accepted distance is strictly below the owner's own
+        const uint32_t at = won ? from : lane;
+        const uint32_t won_triangle = lane_pull(at, res_triangle);
+        const float won_b1 = lane_pull(at, res_b1), won_b2 = lane_pull(at, res_b2);
+        best.far_ = __uint_as_float(nearest);
+        best.triangle = won ? won_triangle & ~kDealExternal : 0xFFFFFFFFu;
+        best.external = (won_triangle & kDealExternal) != 0u;
+        best.b1 = won_b1, best.b2 = won_b2;
+        lr.near_ = own_near;
+    }
+    if (best.triangle != 0xFFFFFFFFu) dealt_hit(lds, item, lr.near_, len, best);
+    return inner;
+}
 template <bool COUNT, bool RCP>
 RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_column, bool scene_fast, uint32_t slot, Counters& cnt) {
     RZ_PHASE(2);
@@ -958,6 +1111,14 @@ RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_c
                 const bool has_b = 2u * p + 1u < count;
                 const uint32_t i = begin + 2u * p;
                 RZ_PHASE(4);
+#ifdef RZ_PHASE_STATS
+                if (!wide && p >= 1u) { RZ_PHASE(9); }
+                if (!wide && p == 1u) {
+                    const uint32_t k = uint32_t(__popcll(__ballot(1)));
+                    RZ_PHASE(10);
+                    if (k <= 12u) { RZ_PHASE(11); } else if (k <= 25u) { RZ_PHASE(12); } else { RZ_PHASE(13); }
+                }
+#endif
                 if constexpr (COUNT) cnt.tri_tests += has_b ? 2u : 1u;
                 tri_pair_step(v3p{f2{v1x.x, v1x.y}, f2{v1y.x, v1y.y}, f2{v1z.x, v1z.y}}, v3p{f2{e1x.x, e1x.y}, f2{e1y.x, e1y.y}, f2{e1z.x, e1z.y}},
                               v3p{f2{e2x.x, e2x.y}, f2{e2y.x, e2y.y}, f2{e2z.x, e2z.y}}, i, has_b, lr, best);
@@ -1310,7 +1471,19 @@ __device__ __forceinline__ int closest_hit_flat(const DScene& s, const FlatWorld
         // C. dense: one lane per item — eight per visit of a wide instance (binned_visit).  The lane that takes item i rotates with the
         //    round and the workgroup, so the busy waves — and with them the SIMDs they live on — change from round to round.
         const uint32_t slot = (tid - ((blockIdx.x + round) & 3u) * 64u) & 255u;
-        if (slot < r.n_items) {
+        const bool has_item = slot < r.n_items;
+        //    A round on one lane per visit: a wave that holds a few visits of long leaves (fw.wide) goes in whole, items or not — its
+        //    idle lanes are there to be dealt those leaves' later pairs (dealt_visit).  Above kDealMaxOwners such visits no trip would fit.
+        //    (A wave's 64 slots are consecutive: the branch is wave-uniform.)
+        bool deal_wave = false;
+        if (!r.split && wave_uniform(slot & ~63u) < r.n_items) {
+            const bool long_leaf = has_item && ((fw.wide >> (lds.items[has_item ? slot : 0u] >> 8)) & 1u) != 0u;
+            const uint32_t owners = uint32_t(__popcll(__ballot(long_leaf)));
+            deal_wave = owners != 0u && owners <= kDealMaxOwners;
+        }
+        bool todo = has_item;
+        if (deal_wave) todo = dealt_visit<COUNT, RCP>(s, lds, scene_fast, slot, has_item, cnt);
+        if (todo) {
             binned_visit<COUNT, RCP>(s, lds, mesh_column, scene_fast, slot, cnt);
         }
         __syncthreads();

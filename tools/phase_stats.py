@@ -11,6 +11,10 @@ NAMES = ["world node box test", "instance box test", "instance entry (to local)"
 # sample_direction (counted in the unit of the kernel that shades — the split pipeline's shade kernel here): the merged sampler's glossy
 # branch, and inside it the powf / acosf / sincosf sequence (RZ_MIRROR_LOBE_CONST: lanes of roughness +-0 take constants instead)
 LOBE_NAMES = {7: "lobe sampler entered", 8: "general glossy sequence"}
+# binned_visit of the one-leaf walk (the trace unit's counters): the pair iterations behind a visit's first on a lane that holds the
+# visit alone, the waves that reach such an iteration with the lanes that hold such a visit then (k), by k, and the dealt trips
+DEAL_NAMES = {9: "later pair, lone-lane visit", 10: "waves with later pairs (k)", 11: "  of those with k <= 12", 12: "  with k 13 - 25",
+              13: "  with k > 25", 14: "dealt trip"}
 for cfgname in sys.argv[1:] or ["D"]:
     preset = scenes.CONFIGS[cfgname]
     w = preset["build"]()
@@ -30,6 +34,10 @@ for cfgname in sys.argv[1:] or ["D"]:
     for k, name in enumerate(NAMES):
         n, lanes = out[2 * k], out[2 * k + 1]
         print(f"  {name:28s} wave executions {n:12d} ({n / waves:8.1f} per wave)  lanes {lanes:13d}  mean active lanes {lanes / max(n, 1):5.1f}")
+    if cfgname in ("A", "B"):
+        for k, name in DEAL_NAMES.items():
+            n, lanes = out[2 * k], out[2 * k + 1]
+            print(f"  {name:28s} wave executions {n:12d} ({n / waves:8.3f} per wave)  lanes {lanes:13d}  mean active lanes {lanes / max(n, 1):5.1f}")
     if hasattr(ctx.lib, "hiprz_read_shadow_phase_stats"):   # the shade unit's counters of the SAME pass (read and cleared)
         ctx.lib.hiprz_read_shadow_phase_stats(out)
         for k, name in LOBE_NAMES.items():
