@@ -422,7 +422,7 @@ RZ_DEV bool zero_or_exponent_in(float x, int lo, int hi) {
     return (__float_as_uint(x) & 0x7FFFFFFFu) == 0u || exponent_in(x, lo, hi);
 }
 #ifdef RZ_PHASE_STATS  // diagnostic build: wave-level executions and active lanes of the MODE 3 walk's steps (tools/phase_stats.py)
-static __device__ unsigned long long rz_phase[32];  // one copy per translation unit: read through that unit's hiprz_read_phase_stats
+static __device__ unsigned long long rz_phase[40];  // one copy per translation unit: read through that unit's hiprz_read_phase_stats
 #define RZ_PHASE(k)                                                                                        \
     do {                                                                                                   \
         const unsigned long long rz_a = __ballot(1);                                                       \
@@ -847,6 +847,7 @@ struct FlatWorld {
     uint32_t ids;         // the leaf's instance ids in leaf order, 4 bits each (flat_pack_id)
     uint32_t count;       // instances in the leaf (<= 8)
     uint32_t wide;        // bit i: instance i's mesh is one leaf of more than 4 triangles — its visits are shared by 8 lanes
+    uint32_t small;       // bit i: instance i's mesh is one leaf of at most 4 triangles — a ray's first visit of it is made in place
 };
 RZ_DEV uint32_t wave_uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 RZ_DEV float wave_uniform(float v) { return __uint_as_float(wave_uniform(__float_as_uint(v))); }
@@ -855,7 +856,7 @@ RZ_DEV float4 wave_uniform(float4 v) { return make_float4(wave_uniform(v.x), wav
 RZ_DEV FlatWorld make_flat_world(const DScene& s) {
     FlatWorld fw;
     fw.root0 = fw.root1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    fw.ids = fw.count = fw.wide = 0u;
+    fw.ids = fw.count = fw.wide = fw.small = 0u;
     if (s.n_instances == 0) return fw;  // uniform
     fw.root0 = wave_uniform(s.nodes[2 * s.tlas_root]), fw.root1 = wave_uniform(s.nodes[2 * s.tlas_root + 1]);
     const uint32_t begin = __float_as_uint(fw.root1.z);
@@ -866,13 +867,15 @@ RZ_DEV FlatWorld make_flat_world(const DScene& s) {
         if (k < fw.count) fw.ids = flat_pack_id(fw.ids, k, wave_uniform(s.tlas_order[begin + k]));
     // Visits of a mesh that is ONE leaf of more than 4 triangles (a Cornell cube: 12) are shared by 8 lanes (closest_hit_binned)
     const uint32_t i = threadIdx.x & 63u;
-    bool wide = false;
+    bool wide = false, small = false;
     if (i < s.n_instances && i < 8u) {
         const uint32_t root = __float_as_uint(s.instances[7 * i].w);
         const uint32_t meta = __float_as_uint(s.nodes[2 * root + 1].w);
         wide = (meta & HIPRZ_NODE_LEAF) != 0u && (meta & HIPRZ_NODE_COUNT_MASK) > 4u;
+        small = (meta & HIPRZ_NODE_LEAF) != 0u && (meta & HIPRZ_NODE_COUNT_MASK) <= 4u;
     }
     fw.wide = uint32_t(__ballot(wide)) & 0xFFu;
+    fw.small = uint32_t(__ballot(small)) & 0xFFu;
     return fw;
 }
 
@@ -1157,6 +1160,57 @@ RZ_DEV void binned_visit(const DScene& s, const BinnedLds& lds, uint32_t* mesh_c
         lds.hit[4 * 256 + src] = inst;
     }
 }
+// A ray's first visit made in place, by the lane that owns the ray, from the registers it still holds (closest_hit_flat, ahead of its
+// rounds): binned_visit's arithmetic on an instance whose mesh is one leaf of at most 4 triangles (FlatWorld::small), operation for
+// operation, with the result in the ray's own column of lds.ray / lds.hit and the range taken back as phase D takes it.  A second
+// inlined copy of the entry and the pair step, as dealt_visit is: through binned_visit's one call site and the ray's LDS slot the
+// flagship kernel spilled 9 more registers and config B gained 0.3 %, against 5.7 % for this form (profiles/r29).
+template <bool COUNT, bool RCP>
+RZ_DEV void first_visit(const DScene& s, const BinnedLds& lds, bool scene_fast, uint32_t inst, WalkRay& g, Counters& cnt) {
+    RZ_PHASE(2);
+    const uint32_t src = threadIdx.x;
+    const InstanceXform x = load_instance_xform(s, inst);
+    WalkRay lr;
+    const float len = to_local<RCP>(x, g, lr, scene_fast);
+    const float4 n0 = s.nodes[2 * x.blas_root], n1 = s.nodes[2 * x.blas_root + 1];
+    RZ_PHASE(3);
+    RZ_COUNT(box_tests);
+    LeafBest best;
+    best.far_ = lr.far_, best.triangle = 0xFFFFFFFFu, best.b1 = best.b2 = 0.0f, best.external = false;
+    if (box_hit_unpacked<RCP>(n0, n1, lr)) {
+        const uint32_t begin = __float_as_uint(n1.z), count = __float_as_uint(n1.w) & HIPRZ_NODE_COUNT_MASK, n_pairs = (count + 1u) >> 1;
+        const unsigned char* section = pair_section(s);
+        const float2* rec = reinterpret_cast<const float2*>(section + 8u * reinterpret_cast<const uint16_t*>(section)[inst]);
+        for (uint32_t p = 0u; p < n_pairs; ++p) {  // at most two
+            const float2* q = rec + p * (RZ_PAIR_RECORD_BYTES / 8u);
+            const float2 v1x = q[0], v1y = q[1], v1z = q[2], e1x = q[3], e1y = q[4], e1z = q[5], e2x = q[6], e2y = q[7], e2z = q[8];
+            const bool has_b = 2u * p + 1u < count;
+            const uint32_t i = begin + 2u * p;
+            RZ_PHASE(4);
+#ifdef RZ_PHASE_STATS
+            if (p >= 1u) {  // (counted as binned_visit counts them)
+                const uint32_t k = uint32_t(__popcll(__ballot(1)));
+                RZ_PHASE(9);
+                RZ_PHASE(10);
+                if (k <= 12u) { RZ_PHASE(11); } else if (k <= 25u) { RZ_PHASE(12); } else { RZ_PHASE(13); }
+            }
+#endif
+            if constexpr (COUNT) cnt.tri_tests += has_b ? 2u : 1u;
+            tri_pair_step(v3p{f2{v1x.x, v1x.y}, f2{v1y.x, v1y.y}, f2{v1z.x, v1z.y}}, v3p{f2{e1x.x, e1x.y}, f2{e1y.x, e1y.y}, f2{e1z.x, e1z.y}},
+                          v3p{f2{e2x.x, e2x.y}, f2{e2y.x, e2y.y}, f2{e2z.x, e2z.y}}, i, has_b, lr, best);
+        }
+    }
+    if (best.triangle != 0xFFFFFFFFu) {
+        g.near_ = lr.near_ / len, g.far_ = best.far_ / len;
+        lds.ray[6 * 256 + src] = g.near_;
+        lds.ray[7 * 256 + src] = g.far_;
+        lds.hit[0 * 256 + src] = best.triangle;
+        lds.hit[1 * 256 + src] = best.external ? 1u : 0u;
+        lds.hit[2 * 256 + src] = __float_as_uint(best.b1);
+        lds.hit[3 * 256 + src] = __float_as_uint(best.b2);
+        lds.hit[4 * 256 + src] = inst;
+    }
+}
 
 // Must be called by ALL 256 threads of the workgroup (it contains barriers); `active` = this lane
 // carries a ray.  Returns 0 / 1 / 2 like closest_hit().
@@ -1417,6 +1471,27 @@ __device__ __forceinline__ int closest_hit_flat(const DScene& s, const FlatWorld
     if (tid < 128u) lds.bins[tid] = 0u;
     __syncthreads();
 
+#ifdef RZ_PHASE_STATS
+    {  // a ray's first candidate: a mesh of one leaf of at most 4 triangles (15), anything else (16)
+        uint32_t peek_mask = flat_mask, peek_next = flat_next;
+        const uint32_t peek = flat_pick(fw.ids, tm, g.far_, peek_mask, peek_next);
+        if (peek != kFlatNone) {
+            if (((fw.small >> peek) & 1u) != 0u) { RZ_PHASE(15); } else { RZ_PHASE(16); }
+        }
+    }
+#endif
+    // The first visit in place: the up-front box tests have told every lane its own first candidate, and where that is a mesh of one
+    // leaf of at most 4 triangles (a wall of a Cornell box: one or two pair trips, the same on every lane, as dense as the rays) binning
+    // it buys nothing.  The lane visits it for its own ray, from the registers it still holds, and the rounds start with the candidate
+    // after it.  No barrier and no atomic: a lane touches its own column of lds.ray / lds.hit alone, which it wrote above, and the first
+    // round's barriers order everything behind it.  `round` stays 0 for the first binned round.  A first candidate of any other kind
+    // is not committed (flat_pick_first) and is picked again by round 0.
+    {
+        const uint32_t first = flat_pick_first(fw.ids, tm, g.far_, flat_mask, flat_next, fw.small);
+        if (__any(first != kFlatNone)) {
+            if (first != kFlatNone) first_visit<COUNT, RCP>(s, lds, scene_fast, first, g, cnt);
+        }
+    }
     const uint32_t lane = tid & 63u;
     const bool wide_bin = ((fw.wide >> (lane & 7u)) & 1u) != 0u;
     while (round < (1u << 20)) {  // workgroup-uniform bound: a ray enters each instance at most once
@@ -1454,6 +1529,10 @@ __device__ __forceinline__ int closest_hit_flat(const DScene& s, const FlatWorld
         const FlatRound r = flat_round(uint32_t(__builtin_amdgcn_readlane(int(incl), 7)));
 #ifdef RZ_PHASE_STATS
         if (!r.split) { RZ_PHASE(6); }  // rounds on the one-lane-per-visit fallback
+        if (round == 0u) {  // the first binned round (17), and whether it is on the fallback (18)
+            RZ_PHASE(17);
+            if (!r.split) { RZ_PHASE(18); }
+        }
 #endif
         const uint32_t before = __shfl(incl - own, int(cand & 7u));
         if (cand != kFlatNone) {

@@ -48,6 +48,24 @@ RZ_DEV uint32_t flat_pick(uint32_t ids, const float (&tm)[8], float far_, uint32
     return kFlatNone;
 }
 
+// flat_pick for the visit a ray makes in place, ahead of the binned rounds: bit i of `small` = instance i's mesh is one leaf of at most
+// 4 triangles.  The candidate is flat_pick's; it is returned, and mask / next committed, only where its bit in `small` is set.
+// Otherwise kFlatNone comes back with mask and next as they were, and the first binned round picks the same candidate again.  A ray
+// without any candidate is finished as flat_pick finishes it.
+RZ_DEV uint32_t flat_pick_first(uint32_t ids, const float (&tm)[8], float far_, uint32_t& mask, uint32_t& next, uint32_t small) {
+    const uint32_t rest = mask & flat_from(next);
+    const uint32_t alive = rest & flat_le_mask(tm, far_);
+    if (alive != 0u) {
+        const uint32_t k = flat_ctz(alive), id = flat_id(ids, k);
+        if (((small >> id) & 1u) == 0u) return kFlatNone;
+        next = k + 1u;
+        return id;
+    }
+    if (rest != 0u) next = flat_top_bit(rest) + 1u;
+    mask = 0u;
+    return kFlatNone;
+}
+
 // ---- one scan for three prefix sums over the (at most 8) bins of a round ----
 // bin k holds c = the lanes its visits want: 8 per visit of a wide instance, 1 otherwise.  Packed: bits 0-11 lanes of the wide bins
 // (<= 256 visits x 8), 12-20 lanes of the other bins (<= 256), 21-29 visits of all bins (<= 256): no field carries into the next.

@@ -43,10 +43,10 @@ void launch_trace(hiprz_ctx* c, const DFrame& f, bool first, bool counted) {
 }  // namespace hiprz
 
 #ifdef RZ_PHASE_STATS  // diagnostic build (tools/phase_stats.py): wave-level executions / active lanes of the walk's step kinds
-extern "C" int hiprz_read_phase_stats(unsigned long long out[32]) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(hiprz::rz_phase), 256);
-    unsigned long long zero[32] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(hiprz::rz_phase), zero, 256);
+extern "C" int hiprz_read_phase_stats(unsigned long long out[40]) {
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(hiprz::rz_phase), sizeof(hiprz::rz_phase));
+    unsigned long long zero[40] = {0};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(hiprz::rz_phase), zero, sizeof(hiprz::rz_phase));
     return 0;
 }
 #endif

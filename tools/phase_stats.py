@@ -15,6 +15,9 @@ LOBE_NAMES = {7: "lobe sampler entered", 8: "general glossy sequence"}
 # visit alone, the waves that reach such an iteration with the lanes that hold such a visit then (k), by k, and the dealt trips
 DEAL_NAMES = {9: "later pair, lone-lane visit", 10: "waves with later pairs (k)", 11: "  of those with k <= 12", 12: "  with k 13 - 25",
               13: "  with k > 25", 14: "dealt trip"}
+# closest_hit_flat ahead of its rounds: the lanes whose first candidate is a mesh of one leaf of at most 4 triangles (FlatWorld::small) and
+# the lanes whose first candidate is anything else; then the first binned round, and how often it is on one lane per visit
+FIRST_NAMES = {15: "first candidate: small leaf", 16: "first candidate: other", 17: "first binned round", 18: "  on one lane per visit"}
 for cfgname in sys.argv[1:] or ["D"]:
     preset = scenes.CONFIGS[cfgname]
     w = preset["build"]()
@@ -25,7 +28,7 @@ for cfgname in sys.argv[1:] or ["D"]:
         ctx.set_traversal_mode(3), ctx.set_pipeline(1), ctx.set_ray_sort(int(os.environ.get('PHASE_RAY_SORT', '0')))
     ctx.set_tree(int(os.environ.get('PHASE_TREE', '4')))   # 4: the Engine hosts' default trees
     ctx.upload_scene(flatten(w)); ctx.upload_camera(camera_struct(w.camera)); ctx.set_config(RenderConfig(tracing=Tracing(preset["max_depth"], 8)).struct())
-    out = (C.c_uint64 * 32)()
+    out = (C.c_uint64 * 40)()
     ctx.render(9); ctx.sync(); ctx.lib.hiprz_read_phase_stats(out)
     if hasattr(ctx.lib, "hiprz_read_shadow_phase_stats"): ctx.lib.hiprz_read_shadow_phase_stats(out)
     ctx.render(1); ctx.sync(); ctx.lib.hiprz_read_phase_stats(out)
@@ -35,7 +38,7 @@ for cfgname in sys.argv[1:] or ["D"]:
         n, lanes = out[2 * k], out[2 * k + 1]
         print(f"  {name:28s} wave executions {n:12d} ({n / waves:8.1f} per wave)  lanes {lanes:13d}  mean active lanes {lanes / max(n, 1):5.1f}")
     if cfgname in ("A", "B"):
-        for k, name in DEAL_NAMES.items():
+        for k, name in {**DEAL_NAMES, **FIRST_NAMES}.items():
             n, lanes = out[2 * k], out[2 * k + 1]
             print(f"  {name:28s} wave executions {n:12d} ({n / waves:8.3f} per wave)  lanes {lanes:13d}  mean active lanes {lanes / max(n, 1):5.1f}")
     if hasattr(ctx.lib, "hiprz_read_shadow_phase_stats"):   # the shade unit's counters of the SAME pass (read and cleared)
