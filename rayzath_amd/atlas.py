@@ -164,12 +164,14 @@ def bake_light(atlas, lighter, rings, seed, lights=None):
     return atlas.read_records(texel_dtype)
 
 
-def bake_bounce(atlas, lighter, gatherer, albedo, emission, bounces, rings, seed, lights, sky, sync):
+def bake_bounce(atlas, lighter, gatherer, albedo, emission, bounces, rings, seed, lights, sky, sync, then=None):
     """the atlas's points light-baked (light.Light `lighter`) and then, `bounces` times: the source albedo * (direct + indirect) + emission
     composed per texel, dilated by `rings` rings and gathered (gather.Gather `gatherer`, its chart map set for this atlas) back at the
     points.  Points, sources and texels stay on the device; albedo and emission are (H, W) arrays of 16-byte records (emission may be
     None).  (direct, indirect, ring) of shape (H, W), both dilated: light.texel_dtype, gather.texel_dtype and the ring map.  `sync` waits
-    for the context's stream."""
+    for the context's stream.  then: called as then(source_ptr) once the last bounce is gathered, with the source that gather read — composed,
+    dilated and still on the device; what it enqueues is waited for with the rest and the value it returns (a function of no arguments
+    is called after the wait) is returned as a fourth item."""
     from . import _hiprt
     from .gather import texel_dtype as gathered_dtype
     from .light import texel_dtype as light_dtype
@@ -196,10 +198,12 @@ def bake_bounce(atlas, lighter, gatherer, albedo, emission, bounces, rings, seed
             atlas.dilate_device(source.ptr, rings)
             gatherer.texels_device(points, n, source.ptr, atlas.width, atlas.height, indirect.ptr, seed, sky)
             gathered = indirect.ptr
+        after = None if then is None else then(source.ptr)
         atlas.dilate_device(direct.ptr, rings)
         atlas.dilate_device(indirect.ptr, rings, ring.ptr)
         sync()
-        return direct.download(shape, light_dtype), indirect.download(shape, gathered_dtype), ring.download(shape, np.uint32)
+        baked = direct.download(shape, light_dtype), indirect.download(shape, gathered_dtype), ring.download(shape, np.uint32)
+        return baked if then is None else baked + (after() if callable(after) else after,)
     finally:
         for b in bufs:
             if b is not None:

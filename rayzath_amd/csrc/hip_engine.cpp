@@ -352,6 +352,7 @@ Engine::~Engine() {
     if (m_atlas) hiprz_atlas_destroy(m_atlas);
     if (m_light) hiprz_light_destroy(m_light);
     if (m_gather) hiprz_gather_destroy(m_gather);
+    if (m_probe) hiprz_probe_destroy(m_probe);
     hiprz_destroy(m_ctx);
 }
 
@@ -575,6 +576,44 @@ hiprz_gather* Engine::gatherer(uint32_t K, uint32_t S, const ChartMap& charts) {
     return m_gather;
 }
 
+std::vector<hiprz_probe_sh> Engine::bakeProbes(const std::vector<hiprz_bake_point>& probes, const std::vector<Record>& source, uint32_t width, uint32_t height,
+                                               const ChartMap& charts, uint32_t K, uint32_t S, uint32_t light_K, uint32_t light_S, uint32_t seed, const float* sky,
+                                               const hiprz_light_range* range, bool direct) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (source.size() != size_t(width) * height) throw Exception(HIPRZ_ERR_INVALID, "bakeProbes: the source is not width x height records");
+    if (!m_probe)
+        if (const int rc = hiprz_probe_create(&m_probe, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_probe_last_error(nullptr));
+    hiprz_probe* p = m_probe;
+    const auto check_probe = [p](int rc) {
+        if (rc != HIPRZ_OK) throw Exception(rc, hiprz_probe_last_error(p));
+    };
+    if (K != m_probe_k || S != m_probe_s) {  // the sphere table of (K, S), kept until another is asked for
+        std::vector<float> table(4 * size_t(K) * S);
+        if (const int rc = hiprz_probe_sphere_directions(K, S, table.data()); rc != HIPRZ_OK) throw Exception(rc, "bakeProbes: K is not one of 16 .. 1024 (powers of two) or S is not in 1..64");
+        check_probe(hiprz_probe_set_directions(p, table.data(), K, S));
+        m_probe_k = K, m_probe_s = S;
+    }
+    if (direct && (light_K != m_probe_light_k || light_S != m_probe_light_s)) {
+        std::vector<float> disk(2 * size_t(light_K) * light_S);
+        if (const int rc = hiprz_light_disk_samples(light_K, light_S, disk.data()); rc != HIPRZ_OK) throw Exception(rc, "bakeProbes: light_K is not a power of two in 1..1024 or light_S is not in 1..64");
+        check_probe(hiprz_probe_set_samples(p, disk.data(), light_K, light_S));
+        m_probe_light_k = light_K, m_probe_light_s = light_S;
+    }
+    check_probe(hiprz_probe_set_charts(p, charts.base.data(), uint32_t(charts.base.size()), charts.uv.data(), uint32_t(charts.uv.size())));
+    std::vector<hiprz_probe_sh> out(probes.size());
+    if (probes.empty()) return out;
+    const float black[3] = {0.0f, 0.0f, 0.0f};
+    check_probe(hiprz_probe_gather_host(p, probes.data(), probes.size(), seed, source.data(), width, height, sky ? sky : black, out.data()));
+    if (direct) check_probe(hiprz_probe_light_host(p, probes.data(), probes.size(), seed, range, out.data(), out.data()));
+    return out;
+}
+
+std::array<float, 3> Engine::probeIrradiance(const hiprz_probe_sh& sh, const float n[3]) {
+    std::array<float, 3> out{};
+    hiprz_probe_irradiance(&sh, n, out.data());
+    return out;
+}
+
 std::vector<hiprz_gather_texel> Engine::gather(const std::vector<hiprz_bake_point>& points, const std::vector<Record>& source, uint32_t width, uint32_t height,
                                                const ChartMap& charts, uint32_t K, uint32_t S, uint32_t seed, const float* sky) {
     std::lock_guard<std::mutex> lock(m_mutex);
@@ -703,6 +742,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_light = nullptr, m_light_k = m_light_s = 0;
                 if (m_gather) hiprz_gather_destroy(m_gather);
                 m_gather = nullptr, m_gather_k = m_gather_s = 0;
+                if (m_probe) hiprz_probe_destroy(m_probe);
+                m_probe = nullptr, m_probe_k = m_probe_s = m_probe_light_k = m_probe_light_s = 0;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

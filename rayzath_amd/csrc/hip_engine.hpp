@@ -28,6 +28,7 @@
 #include "hiprz_gather.h"
 #include "hiprz_light.h"
 #include "hiprz_noise.h"
+#include "hiprz_probe.h"
 #include "hiprz_order.h"
 #include "hiprz_query.h"
 
@@ -303,6 +304,16 @@ public:
     static ChartMap chartMap(const std::vector<AtlasPart>& parts, uint32_t n_instances);
     std::vector<hiprz_gather_texel> gather(const std::vector<hiprz_bake_point>& points, const std::vector<Record>& source, uint32_t width, uint32_t height,
                                            const ChartMap& charts, uint32_t K = 64, uint32_t S = 4, uint32_t seed = 0, const float* sky = nullptr);
+    // Probe baking (include/hiprz_probe.h): per probe of `probes` — a point of free space, its `normal` the axis of its frame — nine
+    // spherical-harmonic coefficients per colour of the light arriving from all directions: the K rays of the sphere table (K, S) read the
+    // width x height atlas `source` through `charts` by the rule of gather, and, with `direct`, the lights of the world of the last
+    // renderWorld call are added with their shadows from the disk table (light_K, light_S), on the device, on top of the gathered records.
+    // The bytes of Context.bake_probes.  Waits for the stream; changes no frame.
+    std::vector<hiprz_probe_sh> bakeProbes(const std::vector<hiprz_bake_point>& probes, const std::vector<Record>& source, uint32_t width, uint32_t height,
+                                           const ChartMap& charts, uint32_t K = 64, uint32_t S = 4, uint32_t light_K = 16, uint32_t light_S = 4, uint32_t seed = 0,
+                                           const float* sky = nullptr, const hiprz_light_range* range = nullptr, bool direct = true);
+    // E(n) of one record for the unit normal n (hiprz_probe_irradiance): what a lightmap texel with that normal would hold at the probe
+    static std::array<float, 3> probeIrradiance(const hiprz_probe_sh& sh, const float n[3]);
     // bakeLightAtlas and then `bounces` radiosity steps: the source albedo * (direct + indirect) + emission per texel (emission may be
     // empty: 0), `rings` rings of dilation, and the gather at the atlas's points.  `direct` and `indirect` come back dilated, with the ring
     // map of bakeLightAtlas.  This host has no device allocator of its own: the steps go through the libraries' host-pointer calls, and
@@ -370,6 +381,8 @@ private:
     hiprz_light* m_light = nullptr;         // bound to m_ctx, created at the first light bake; it holds the disk table of (m_light_k, m_light_s)
     uint32_t m_light_k = 0, m_light_s = 0;
     hiprz_light* lighter(uint32_t K, uint32_t S);  // m_light holding the disk table of (K, S)
+    hiprz_probe* m_probe = nullptr;         // bound to m_ctx, created at the first bakeProbes; it holds the sphere table of (m_probe_k, m_probe_s) and the disk table
+    uint32_t m_probe_k = 0, m_probe_s = 0, m_probe_light_k = 0, m_probe_light_s = 0;
     hiprz_gather* m_gather = nullptr;       // bound to m_ctx, created at the first gather; it holds the cosine table of (m_gather_k, m_gather_s)
     uint32_t m_gather_k = 0, m_gather_s = 0;
     hiprz_gather* gatherer(uint32_t K, uint32_t S, const ChartMap& charts);  // m_gather holding the cosine table of (K, S) and `charts`

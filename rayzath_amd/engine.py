@@ -146,6 +146,9 @@ class Context:
         if getattr(self, "_gather", None) is not None:
             self._gather.close()
             self._gather = None
+        if getattr(self, "_probe", None) is not None:
+            self._probe.close()
+            self._probe = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -608,6 +611,10 @@ class Context:
         width), both dilated — light.texel_dtype, gather.texel_dtype and the ring map of bake_light_atlas; albedo * (direct.light +
         indirect.mean) + emission is what a texel sends on.  Points, sources and texels never visit the host between the steps.  Waits for
         the stream; changes no frame."""
+        return self._bake_bounce(parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, None)
+
+    def _bake_bounce(self, parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, then):
+        """the one path of bake_bounce_atlas and bake_probe_field: atlas.bake_bounce on this context's handles, `then` handed through"""
         from . import atlas as _atlas
         from . import gather as _gather
         shape = (height, width)
@@ -616,7 +623,69 @@ class Context:
         a, h = self.atlas(), self._light_with(samples)
         _atlas.build(a, parts, width, height, near, far)
         g = self._gather_with(directions, _gather.chart_tables(parts, getattr(self, "_n_instances", 0)))
-        return _atlas.bake_bounce(a, h, g, albedo, emission, bounces, rings, seed, lights, sky, self.sync)
+        return _atlas.bake_bounce(a, h, g, albedo, emission, bounces, rings, seed, lights, sky, self.sync, then)
+
+    # --- probe baking: the light arriving at points of free space as spherical-harmonic coefficients (include/hiprz_probe.h) ---
+    def prober(self):
+        """the context's probe.Probe, created at the first use (device-pointer calls: gather_device, light_device, samples_device)"""
+        from . import probe as _probe
+        if getattr(self, "_probe", None) is None:
+            self._probe = _probe.Probe(self._ctx)
+        return self._probe
+
+    def _probe_with(self, directions, samples, charts):
+        p = self.prober()
+        if directions is not None and not (isinstance(directions, tuple) and directions == p.table):       # a sphere table already set is not set again
+            p.set_directions(directions)
+        if samples is not None and not (isinstance(samples, tuple) and samples == p.disk):
+            p.set_samples(samples)
+        if charts is not None:
+            p.set_charts(*charts)
+        return p
+
+    def bake_probes(self, probes, source, width, height, charts, directions=(64, 4), samples=(16, 4), seed=0, sky=(0.0, 0.0, 0.0), lights=None, direct=True):
+        """The light arriving at every probe of `probes` (an array of bake.point_dtype: position, near, frame axis, far) from all
+        directions: an array of probe.sh_dtype of the same shape — nine spherical-harmonic coefficients per colour, the mean over the K
+        rays of the probe of what the width x height atlas `source` holds under each ray's closest hit (the rule of gather) times the
+        basis, plus, with `direct`, the scene's spot and direct lights with their shadows (the sampling of bake_light without its cosine).
+        probe.irradiance(sh, n) then approximates bake_light(...).light + gather(...).mean of a surface point there with normal n.
+        directions: a (K, S) pair for the sphere table, an (S, K, 4) array or None for the table set before; samples: as for bake_light;
+        charts: (base, uv) of gather.chart_tables(parts, n_instances), or None for the map set before; lights: as for bake_light.
+        sh[0].w is rays that read a texel | rays that missed << 16 (probe.INVALID for an invalid probe), sh[1].w the shadowed rays.  The
+        records never visit the host between the two launches.  Waits for the stream; changes no frame."""
+        p = self._probe_with(directions, samples if direct else None, charts)
+        return p.bake(probes, source, width, height, seed, sky, lights, direct, self.sync)
+
+    def probe_samples(self, probes, seed=0, directions=None, charts=None):
+        """What bake_probes walks for `probes` under the table and the chart map set before (or `directions`, `charts`):
+        gather.sample_dtype of shape probes.shape + (K,), the records gather_samples writes for the same points, table, seed and map."""
+        return self._probe_with(directions, None, charts).samples(probes, seed, self.sync)
+
+    def bake_probe_field(self, parts, width, height, albedo, emission, bounces, probes, directions=(64, 4), samples=(16, 4), seed=0, rings=2, sky=(0.0, 0.0, 0.0),
+                         near=1.0e-3, far=3.0e38, lights=None, probe_directions=(64, 4), direct=True):
+        """bake_bounce_atlas and, while the source of its last gather — albedo * (direct + indirect of the bounce before) + emission,
+        dilated — is still on the device, bake_probes of `probes` from it: (direct, indirect, ring, sh), the first three what
+        bake_bounce_atlas returns in every byte, sh of probe.sh_dtype in the shape of `probes`.  probe_directions: the probes' table, a
+        (K, S) pair for the sphere table or an (S, K, 4) array.  Waits for the stream; changes no frame."""
+        from . import _hiprt
+        from . import gather as _gather
+        from . import probe as _probe
+        probes = _probe.Probe._probes(probes)
+        p = self._probe_with(probe_directions, samples if direct else None, _gather.chart_tables(parts, getattr(self, "_n_instances", 0)))
+        bufs = []
+
+        def then(source_ptr):
+            if probes.size == 0:
+                return np.zeros(probes.shape, _probe.sh_dtype)
+            bufs.extend([_hiprt.DeviceBuffer.of(probes), _hiprt.DeviceBuffer(probes.size * _probe.sh_dtype.itemsize)])
+            p.bake_device(bufs[0].ptr, probes.size, source_ptr, width, height, bufs[1].ptr, seed, sky, lights, direct)
+            return lambda: bufs[1].download(probes.shape, _probe.sh_dtype)
+
+        try:
+            return self._bake_bounce(parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, then)
+        finally:
+            for b in bufs:
+                b.free()
 
     def pixel_rays(self):
         """(H, W) array of query.ray_dtype: the selected camera's pixel-centre rays, the ones the first pass, the guides and ray_cast walk"""
