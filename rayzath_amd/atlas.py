@@ -155,23 +155,28 @@ def bake(atlas, baker, rings, seed):
     return atlas.read_records(texel_dtype)
 
 
-def bake_light(atlas, lighter, rings, seed, lights=None):
+def bake_light(atlas, lighter, rings, seed, lights=None, smoother=None, smooth=None):
     """the atlas's points light-baked (light.Light `lighter`) where they lie, into the handle's own records, and those dilated by `rings`
-    rings: (texels, ring) of shape (H, W).  Waits for the context's stream."""
+    rings: (texels, ring) of shape (H, W).  smooth: None, or the params of smooth.Smooth `smoother`, which then smooths the records in
+    place between the bake and the dilation.  Waits for the context's stream."""
     from .light import texel_dtype
     lighter.bake_device(atlas.points_device(), atlas.width * atlas.height, atlas.records_device(), seed, lights)
+    if smooth is not None:
+        smoother.texels_device(atlas.points_device(), atlas.records_device(), atlas.width, atlas.height, smooth)
     atlas.dilate_device(atlas.records_device(), rings)
     return atlas.read_records(texel_dtype)
 
 
-def bake_bounce(atlas, lighter, gatherer, albedo, emission, bounces, rings, seed, lights, sky, sync, then=None):
+def bake_bounce(atlas, lighter, gatherer, albedo, emission, bounces, rings, seed, lights, sky, sync, then=None, smoother=None, smooth=None):
     """the atlas's points light-baked (light.Light `lighter`) and then, `bounces` times: the source albedo * (direct + indirect) + emission
     composed per texel, dilated by `rings` rings and gathered (gather.Gather `gatherer`, its chart map set for this atlas) back at the
     points.  Points, sources and texels stay on the device; albedo and emission are (H, W) arrays of 16-byte records (emission may be
     None).  (direct, indirect, ring) of shape (H, W), both dilated: light.texel_dtype, gather.texel_dtype and the ring map.  `sync` waits
     for the context's stream.  then: called as then(source_ptr) once the last bounce is gathered, with the source that gather read — composed,
     dilated and still on the device; what it enqueues is waited for with the rest and the value it returns (a function of no arguments
-    is called after the wait) is returned as a fourth item."""
+    is called after the wait) is returned as a fourth item.  smooth: None, or the params of smooth.Smooth `smoother`, which then smooths
+    in place, where they lie: direct once, right after its bake (before any source is composed from it, and so before its dilation), and
+    every bounce's indirect right after its gather (before it is composed into the next source; the last before its dilation)."""
     from . import _hiprt
     from .gather import texel_dtype as gathered_dtype
     from .light import texel_dtype as light_dtype
@@ -192,11 +197,15 @@ def bake_bounce(atlas, lighter, gatherer, albedo, emission, bounces, rings, seed
         bufs.append(d_emission)
         points = atlas.points_device()
         lighter.bake_device(points, n, direct.ptr, seed, lights)
+        if smooth is not None:
+            smoother.texels_device(points, direct.ptr, atlas.width, atlas.height, smooth)
         gathered = None
         for _ in range(bounces):
             gatherer.compose_device(direct.ptr, gathered, d_albedo.ptr, None if d_emission is None else d_emission.ptr, source.ptr, n)
             atlas.dilate_device(source.ptr, rings)
             gatherer.texels_device(points, n, source.ptr, atlas.width, atlas.height, indirect.ptr, seed, sky)
+            if smooth is not None:
+                smoother.texels_device(points, indirect.ptr, atlas.width, atlas.height, smooth)
             gathered = indirect.ptr
         after = None if then is None else then(source.ptr)
         atlas.dilate_device(direct.ptr, rings)

@@ -353,6 +353,7 @@ Engine::~Engine() {
     if (m_light) hiprz_light_destroy(m_light);
     if (m_gather) hiprz_gather_destroy(m_gather);
     if (m_probe) hiprz_probe_destroy(m_probe);
+    if (m_smooth) hiprz_smooth_destroy(m_smooth);
     hiprz_destroy(m_ctx);
 }
 
@@ -527,7 +528,7 @@ hiprz_atlas* Engine::atlasWith(const std::vector<AtlasPart>& parts, uint32_t wid
 }
 
 Engine::LitAtlas Engine::bakeLightAtlas(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, uint32_t K, uint32_t S, uint32_t seed, uint32_t rings,
-                                        float near_, float far_, const hiprz_light_range* range) {
+                                        float near_, float far_, const hiprz_light_range* range, const hiprz_smooth_params* smooth) {
     std::lock_guard<std::mutex> lock(m_mutex);
     if (parts.empty()) throw Exception(HIPRZ_ERR_INVALID, "bakeLightAtlas: an atlas needs at least one part");
     hiprz_light* l = lighter(K, S);
@@ -540,12 +541,31 @@ Engine::LitAtlas Engine::bakeLightAtlas(const std::vector<AtlasPart>& parts, uin
     void* records = hiprz_atlas_records_device(m_atlas);
     if (const int rc = hiprz_light_bake(l, hiprz_atlas_points_device(m_atlas), texels, seed, range, static_cast<hiprz_light_texel*>(records), nullptr); rc != HIPRZ_OK)
         throw Exception(rc, hiprz_light_last_error(l));
+    if (smooth)  // in place, between the bake and the dilation: the gutters take smoothed values
+        if (const int rc = hiprz_smooth_texels(smoother(), hiprz_atlas_points_device(m_atlas), records, width, height, smooth, records, nullptr); rc != HIPRZ_OK)
+            throw Exception(rc, hiprz_smooth_last_error(m_smooth));
     atlas_check(hiprz_atlas_dilate(m_atlas, records, rings, nullptr, nullptr));
     LitAtlas out;
     out.width = width, out.height = height;
     out.texels.resize(texels), out.samples.resize(texels), out.ring.resize(texels);
     atlas_check(hiprz_atlas_read_records_host(m_atlas, out.texels.data(), out.ring.data()));
     atlas_check(hiprz_atlas_read_host(m_atlas, nullptr, out.samples.data()));
+    return out;
+}
+
+hiprz_smooth* Engine::smoother() {
+    if (!m_smooth)
+        if (const int rc = hiprz_smooth_create(&m_smooth, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_smooth_last_error(nullptr));
+    return m_smooth;
+}
+
+std::vector<Engine::Record> Engine::smoothTexels(const std::vector<hiprz_bake_point>& points, const std::vector<Record>& records, uint32_t width, uint32_t height,
+                                                 const hiprz_smooth_params& params) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (points.size() != size_t(width) * height || records.size() != points.size()) throw Exception(HIPRZ_ERR_INVALID, "smoothTexels: points and records are width x height each");
+    std::vector<Record> out(records.size());
+    if (const int rc = hiprz_smooth_texels_host(smoother(), points.data(), records.data(), width, height, &params, out.data()); rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_smooth_last_error(m_smooth));
     return out;
 }
 
@@ -629,7 +649,7 @@ std::vector<hiprz_gather_texel> Engine::gather(const std::vector<hiprz_bake_poin
 
 Engine::BouncedAtlas Engine::bakeBounceAtlas(const std::vector<AtlasPart>& parts, uint32_t n_instances, uint32_t width, uint32_t height, const std::vector<Record>& albedo,
                                              const std::vector<Record>& emission, uint32_t bounces, uint32_t K, uint32_t S, uint32_t light_K, uint32_t light_S, uint32_t seed,
-                                             uint32_t rings, const float* sky, float near_, float far_) {
+                                             uint32_t rings, const float* sky, float near_, float far_, const hiprz_smooth_params* smooth) {
     std::lock_guard<std::mutex> lock(m_mutex);
     const size_t texels = size_t(width) * height;
     if (parts.empty()) throw Exception(HIPRZ_ERR_INVALID, "bakeBounceAtlas: an atlas needs at least one part");
@@ -650,12 +670,20 @@ Engine::BouncedAtlas Engine::bakeBounceAtlas(const std::vector<AtlasPart>& parts
     out.width = width, out.height = height;
     out.direct.resize(texels), out.indirect.resize(texels), out.ring.resize(texels);
     if (const int rc = hiprz_light_bake_host(l, points.data(), texels, seed, nullptr, out.direct.data()); rc != HIPRZ_OK) throw Exception(rc, hiprz_light_last_error(l));
+    // with `smooth`: direct once, right after its bake, and every bounce's indirect right after its gather, in place
+    const auto smoothed = [&](void* records) {
+        if (!smooth) return;
+        if (const int rc = hiprz_smooth_texels_host(smoother(), points.data(), records, width, height, smooth, records); rc != HIPRZ_OK)
+            throw Exception(rc, hiprz_smooth_last_error(m_smooth));
+    };
+    smoothed(out.direct.data());
     const float black[3] = {0.0f, 0.0f, 0.0f};
     std::vector<Record> source(texels);
     for (uint32_t b = 0; b < bounces; ++b) {
         gather_check(hiprz_gather_compose_host(g, out.direct.data(), b ? out.indirect.data() : nullptr, albedo.data(), emission.empty() ? nullptr : emission.data(), source.data(), texels));
         atlas_check(hiprz_atlas_dilate_host(m_atlas, source.data(), rings, nullptr));
         gather_check(hiprz_gather_texels_host(g, points.data(), texels, seed, source.data(), width, height, sky ? sky : black, out.indirect.data()));
+        smoothed(out.indirect.data());
     }
     atlas_check(hiprz_atlas_dilate_host(m_atlas, out.direct.data(), rings, nullptr));
     atlas_check(hiprz_atlas_dilate_host(m_atlas, out.indirect.data(), rings, out.ring.data()));
@@ -744,6 +772,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_gather = nullptr, m_gather_k = m_gather_s = 0;
                 if (m_probe) hiprz_probe_destroy(m_probe);
                 m_probe = nullptr, m_probe_k = m_probe_s = m_probe_light_k = m_probe_light_s = 0;
+                if (m_smooth) hiprz_smooth_destroy(m_smooth);
+                m_smooth = nullptr;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

@@ -29,6 +29,7 @@
 #include "hiprz_light.h"
 #include "hiprz_noise.h"
 #include "hiprz_probe.h"
+#include "hiprz_smooth.h"
 #include "hiprz_order.h"
 #include "hiprz_query.h"
 
@@ -280,6 +281,7 @@ public:
     std::vector<hiprz_light_texel> bakeLight(const std::vector<hiprz_bake_point>& points, uint32_t K = 16, uint32_t S = 4, uint32_t seed = 0,
                                              const hiprz_light_range* range = nullptr);
     // bakeAtlas with bakeLight's quantity per texel: atlas points, the light bake where they lie on the device, `rings` rings of dilation.
+    // smooth: nullptr, or the params of smoothTexels, run on the device between the bake and the dilation.
     struct LitAtlas {
         uint32_t width = 0, height = 0;
         std::vector<hiprz_light_texel> texels;
@@ -287,7 +289,7 @@ public:
         std::vector<uint32_t> ring;
     };
     LitAtlas bakeLightAtlas(const std::vector<AtlasPart>& parts, uint32_t width, uint32_t height, uint32_t K = 16, uint32_t S = 4, uint32_t seed = 0, uint32_t rings = 2,
-                            float near_ = 1.0e-3f, float far_ = 3.0e38f, const hiprz_light_range* range = nullptr);
+                            float near_ = 1.0e-3f, float far_ = 3.0e38f, const hiprz_light_range* range = nullptr, const hiprz_smooth_params* smooth = nullptr);
     // Bounce baking (include/hiprz_gather.h): per surface point of `points`, the mean over the K hemisphere rays of the cosine table (K, S) of
     // what the width x height atlas `source` (16-byte records: RGB and a word, HIPRZ_GATHER_INVALID where a texel has no value) holds under
     // each ray's closest hit in the world of the last renderWorld call; `sky` (three floats, nullptr: 0) for a ray that hits nothing.  The
@@ -317,7 +319,8 @@ public:
     // bakeLightAtlas and then `bounces` radiosity steps: the source albedo * (direct + indirect) + emission per texel (emission may be
     // empty: 0), `rings` rings of dilation, and the gather at the atlas's points.  `direct` and `indirect` come back dilated, with the ring
     // map of bakeLightAtlas.  This host has no device allocator of its own: the steps go through the libraries' host-pointer calls, and
-    // give the bytes of Context.bake_bounce_atlas, which keeps everything on the device.
+    // give the bytes of Context.bake_bounce_atlas, which keeps everything on the device.  smooth: nullptr, or the params of smoothTexels:
+    // direct is smoothed once right after its bake and every bounce's indirect right after its gather.
     struct BouncedAtlas {
         uint32_t width = 0, height = 0;
         std::vector<hiprz_light_texel> direct;
@@ -326,7 +329,14 @@ public:
     };
     BouncedAtlas bakeBounceAtlas(const std::vector<AtlasPart>& parts, uint32_t n_instances, uint32_t width, uint32_t height, const std::vector<Record>& albedo,
                                  const std::vector<Record>& emission, uint32_t bounces = 1, uint32_t K = 64, uint32_t S = 4, uint32_t light_K = 16, uint32_t light_S = 4,
-                                 uint32_t seed = 0, uint32_t rings = 2, const float* sky = nullptr, float near_ = 1.0e-3f, float far_ = 3.0e38f);
+                                 uint32_t seed = 0, uint32_t rings = 2, const float* sky = nullptr, float near_ = 1.0e-3f, float far_ = 3.0e38f,
+                                 const hiprz_smooth_params* smooth = nullptr);
+    // Lightmap smoothing (include/hiprz_smooth.h): the width x height records of an atlas (RGB and a word: light or gather texels)
+    // smoothed along its surfaces under the guidance of the atlas's points, by an a-trous filter of params.iterations steps that never
+    // blends a texel with a neighbour of the atlas that is not its neighbour on the surface.  A texel without a value keeps its 16 bytes;
+    // every word comes back unchanged.  The bytes of Context.smooth_texels.  Waits for the stream; changes no frame.
+    std::vector<Record> smoothTexels(const std::vector<hiprz_bake_point>& points, const std::vector<Record>& records, uint32_t width, uint32_t height,
+                                     const hiprz_smooth_params& params);
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -381,6 +391,8 @@ private:
     hiprz_light* m_light = nullptr;         // bound to m_ctx, created at the first light bake; it holds the disk table of (m_light_k, m_light_s)
     uint32_t m_light_k = 0, m_light_s = 0;
     hiprz_light* lighter(uint32_t K, uint32_t S);  // m_light holding the disk table of (K, S)
+    hiprz_smooth* m_smooth = nullptr;       // bound to m_ctx, created at the first smoothing
+    hiprz_smooth* smoother();               // m_smooth, created when there is none
     hiprz_probe* m_probe = nullptr;         // bound to m_ctx, created at the first bakeProbes; it holds the sphere table of (m_probe_k, m_probe_s) and the disk table
     uint32_t m_probe_k = 0, m_probe_s = 0, m_probe_light_k = 0, m_probe_light_s = 0;
     hiprz_gather* m_gather = nullptr;       // bound to m_ctx, created at the first gather; it holds the cosine table of (m_gather_k, m_gather_s)

@@ -149,6 +149,9 @@ class Context:
         if getattr(self, "_probe", None) is not None:
             self._probe.close()
             self._probe = None
+        if getattr(self, "_smooth", None) is not None:
+            self._smooth.close()
+            self._smooth = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -561,14 +564,16 @@ class Context:
         query.ray_dtype and float32 of shape points.shape + (L, K), spot lights first; a skipped sample reads direction 0 and weight 0."""
         return self._light_with(samples).rays(points, seed, lights, self.sync)
 
-    def bake_light_atlas(self, parts, width, height, samples=(16, 4), seed=0, rings=2, near=1.0e-3, far=3.0e38, lights=None):
+    def bake_light_atlas(self, parts, width, height, samples=(16, 4), seed=0, rings=2, near=1.0e-3, far=3.0e38, lights=None, smooth=None):
         """atlas_points, bake_light of the points where they lie on the device, and `rings` rings of gutter dilation: (texels, samples,
         ring) of shape (height, width) — light.texel_dtype, atlas.sample_dtype and uint32 (0 covered, r filled in ring r, atlas.NONE still
-        empty).  Texel (x, y) is point y * width + x of the bake.  Waits for the stream; changes no frame."""
+        empty).  Texel (x, y) is point y * width + x of the bake.  smooth: None, or smooth.params(...) (or a dict of its keywords) for
+        smooth_texels of the baked light on the device before the dilation, so that the gutters take smoothed values.  Waits for the
+        stream; changes no frame."""
         from . import atlas as _atlas
         a, h = self.atlas(), self._light_with(samples)
         _atlas.build(a, parts, width, height, near, far)
-        texels, ring = _atlas.bake_light(a, h, rings, seed, lights)
+        texels, ring = _atlas.bake_light(a, h, rings, seed, lights, *self._smooth_with(smooth))
         return texels, a.read(points=False)[1], ring
 
     # --- bounce baking: the light an atlas holds, gathered over the hemisphere of a surface point (include/hiprz_gather.h) ---
@@ -604,16 +609,18 @@ class Context:
         return self._gather_with(directions, charts).samples(points, seed, self.sync)
 
     def bake_bounce_atlas(self, parts, width, height, albedo, emission=None, bounces=1, directions=(64, 4), samples=(16, 4), seed=0, rings=2, sky=(0.0, 0.0, 0.0),
-                          near=1.0e-3, far=3.0e38, lights=None):
+                          near=1.0e-3, far=3.0e38, lights=None, smooth=None):
         """atlas_points, bake_light of the points and then `bounces` radiosity steps on the device: the source albedo * (direct + indirect)
         + emission per texel, `rings` rings of gutter dilation, and gather at the points.  albedo and emission: a colour (3,), an
         (height, width, 3) array or (height, width) 16-byte records; emission None is 0.  (direct, indirect, ring) of shape (height,
         width), both dilated — light.texel_dtype, gather.texel_dtype and the ring map of bake_light_atlas; albedo * (direct.light +
-        indirect.mean) + emission is what a texel sends on.  Points, sources and texels never visit the host between the steps.  Waits for
-        the stream; changes no frame."""
-        return self._bake_bounce(parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, None)
+        indirect.mean) + emission is what a texel sends on.  smooth: None, or smooth.params(...) (or a dict of its keywords): direct is then
+        smoothed once right after its bake, and every bounce's indirect right after its gather — before it is composed into the next
+        source, the last before its dilation — so that no bounce feeds its noise into the next.  Points, sources and texels never visit
+        the host between the steps.  Waits for the stream; changes no frame."""
+        return self._bake_bounce(parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, None, smooth)
 
-    def _bake_bounce(self, parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, then):
+    def _bake_bounce(self, parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, then, smooth=None):
         """the one path of bake_bounce_atlas and bake_probe_field: atlas.bake_bounce on this context's handles, `then` handed through"""
         from . import atlas as _atlas
         from . import gather as _gather
@@ -623,7 +630,31 @@ class Context:
         a, h = self.atlas(), self._light_with(samples)
         _atlas.build(a, parts, width, height, near, far)
         g = self._gather_with(directions, _gather.chart_tables(parts, getattr(self, "_n_instances", 0)))
-        return _atlas.bake_bounce(a, h, g, albedo, emission, bounces, rings, seed, lights, sky, self.sync, then)
+        return _atlas.bake_bounce(a, h, g, albedo, emission, bounces, rings, seed, lights, sky, self.sync, then, *self._smooth_with(smooth))
+
+    # --- lightmap smoothing: an edge-stopping filter over an atlas's records, guided by its surface points (include/hiprz_smooth.h) ---
+    def smoother(self):
+        """the context's smooth.Smooth, created at the first use (device-pointer call: texels_device)"""
+        from . import smooth as _smooth
+        if getattr(self, "_smooth", None) is None:
+            self._smooth = _smooth.Smooth(self._ctx)
+        return self._smooth
+
+    def _smooth_with(self, smooth):
+        """(handle, params record) of a bake's `smooth` keyword; (None, None) for None, which loads and runs no smoothing code"""
+        if smooth is None:
+            return None, None
+        from . import smooth as _smooth
+        return self.smoother(), _smooth._params(smooth)
+
+    def smooth_texels(self, points, records, params=None):
+        """The records of an atlas smoothed along its surfaces: `points` (height, width) of bake.point_dtype (atlas_points), `records`
+        (height, width) of a 16-byte dtype — three floats and a word, light.texel_dtype or gather.texel_dtype — and `params` a
+        smooth.params(...) record, a dict of its keywords or None for its defaults.  A texel whose word is smooth.INVALID, whose point has
+        no normal or whose floats are not finite keeps its 16 bytes and enters no mean; every word comes back unchanged.  An array like
+        `records`.  Waits for the stream; changes no frame."""
+        from . import smooth as _smooth
+        return self.smoother().texels(points, records, _smooth.params() if params is None else params)
 
     # --- probe baking: the light arriving at points of free space as spherical-harmonic coefficients (include/hiprz_probe.h) ---
     def prober(self):
@@ -662,11 +693,11 @@ class Context:
         return self._probe_with(directions, None, charts).samples(probes, seed, self.sync)
 
     def bake_probe_field(self, parts, width, height, albedo, emission, bounces, probes, directions=(64, 4), samples=(16, 4), seed=0, rings=2, sky=(0.0, 0.0, 0.0),
-                         near=1.0e-3, far=3.0e38, lights=None, probe_directions=(64, 4), direct=True):
+                         near=1.0e-3, far=3.0e38, lights=None, probe_directions=(64, 4), direct=True, smooth=None):
         """bake_bounce_atlas and, while the source of its last gather — albedo * (direct + indirect of the bounce before) + emission,
         dilated — is still on the device, bake_probes of `probes` from it: (direct, indirect, ring, sh), the first three what
         bake_bounce_atlas returns in every byte, sh of probe.sh_dtype in the shape of `probes`.  probe_directions: the probes' table, a
-        (K, S) pair for the sphere table or an (S, K, 4) array.  Waits for the stream; changes no frame."""
+        (K, S) pair for the sphere table or an (S, K, 4) array.  smooth: as for bake_bounce_atlas.  Waits for the stream; changes no frame."""
         from . import _hiprt
         from . import gather as _gather
         from . import probe as _probe
@@ -682,7 +713,7 @@ class Context:
             return lambda: bufs[1].download(probes.shape, _probe.sh_dtype)
 
         try:
-            return self._bake_bounce(parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, then)
+            return self._bake_bounce(parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, then, smooth)
         finally:
             for b in bufs:
                 b.free()
