@@ -92,9 +92,11 @@
  * Left out on purpose:
  *   - bands above 2;
  *   - ringing windowing: the coefficients are the plain projection;
- *   - probe placement and visibility: a probe inside geometry sees back faces (+0), a probe behind a wall leaks through interpolation;
+ *   - probe placement and visibility: a probe inside geometry sees back faces (+0), a probe behind a wall leaks through a plain
+ *     interpolation — include/hiprz_field.h bakes a visibility map per probe and weights the blend by it;
  *   - glossy transport, transmission and the scattering medium, as the gather leaves them out;
- *   - a device-side evaluation kernel: the evaluation is nine multiply-adds a shader writes itself.
+ *   - a device-side evaluation kernel: the evaluation is nine multiply-adds a shader writes itself; the lookup of a whole grid of
+ *     probes for shaded points on the device is include/hiprz_field.h's.
  *
  * THE KERNELS, 64 threads per workgroup (one wave), no atomics.  rz_probe_gather_kernel and rz_probe_light_kernel have the shapes of
  * rz_gather_kernel and rz_light_bake_kernel: for K >= 64 one wave takes one probe in K / 64 rounds (per light); for K < 64 one wave takes

@@ -354,6 +354,7 @@ Engine::~Engine() {
     if (m_gather) hiprz_gather_destroy(m_gather);
     if (m_probe) hiprz_probe_destroy(m_probe);
     if (m_smooth) hiprz_smooth_destroy(m_smooth);
+    if (m_field) hiprz_field_destroy(m_field);
     hiprz_destroy(m_ctx);
 }
 
@@ -634,6 +635,40 @@ std::array<float, 3> Engine::probeIrradiance(const hiprz_probe_sh& sh, const flo
     return out;
 }
 
+hiprz_field* Engine::fielder() {
+    if (!m_field)
+        if (const int rc = hiprz_field_create(&m_field, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_field_last_error(nullptr));
+    return m_field;
+}
+
+std::vector<hiprz_field_vis> Engine::bakeVisibility(const std::vector<hiprz_bake_point>& probes, float reach, uint32_t K, uint32_t S, uint32_t seed) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    hiprz_field* f = fielder();
+    if (K != m_field_k || S != m_field_s) {  // the sphere table of (K, S), kept until another is asked for
+        std::vector<float> table(4 * size_t(K) * S);
+        if (const int rc = hiprz_probe_sphere_directions(K, S, table.data()); rc != HIPRZ_OK) throw Exception(rc, "bakeVisibility: K is not one of 64 .. 1024 (powers of two) or S is not in 1..64");
+        if (const int rc = hiprz_field_set_directions(f, table.data(), K, S); rc != HIPRZ_OK) throw Exception(rc, hiprz_field_last_error(f));
+        m_field_k = K, m_field_s = S;
+    }
+    std::vector<hiprz_field_vis> out(probes.size());
+    if (probes.empty()) return out;
+    if (const int rc = hiprz_field_visibility_host(f, probes.data(), probes.size(), seed, reach, out.data()); rc != HIPRZ_OK) throw Exception(rc, hiprz_field_last_error(f));
+    return out;
+}
+
+std::vector<hiprz_field_result> Engine::lookupField(const hiprz_field_grid& grid, const std::vector<hiprz_bake_point>& probes, const std::vector<hiprz_probe_sh>& sh,
+                                                    const std::vector<hiprz_field_vis>& vis, const std::vector<hiprz_bake_point>& points, const hiprz_field_params& params) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (sh.size() != probes.size() || (!vis.empty() && vis.size() != probes.size())) throw Exception(HIPRZ_ERR_INVALID, "lookupField: one record per probe");
+    hiprz_field* f = fielder();
+    std::vector<hiprz_field_result> out(points.size());
+    if (points.empty()) return out;
+    if (const int rc = hiprz_field_lookup_host(f, &grid, probes.data(), sh.data(), vis.empty() ? nullptr : vis.data(), probes.size(), &params, points.data(), points.size(), out.data());
+        rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_field_last_error(f));
+    return out;
+}
+
 std::vector<hiprz_gather_texel> Engine::gather(const std::vector<hiprz_bake_point>& points, const std::vector<Record>& source, uint32_t width, uint32_t height,
                                                const ChartMap& charts, uint32_t K, uint32_t S, uint32_t seed, const float* sky) {
     std::lock_guard<std::mutex> lock(m_mutex);
@@ -774,6 +809,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_probe = nullptr, m_probe_k = m_probe_s = m_probe_light_k = m_probe_light_s = 0;
                 if (m_smooth) hiprz_smooth_destroy(m_smooth);
                 m_smooth = nullptr;
+                if (m_field) hiprz_field_destroy(m_field);
+                m_field = nullptr, m_field_k = m_field_s = 0;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

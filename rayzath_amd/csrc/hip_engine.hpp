@@ -30,6 +30,7 @@
 #include "hiprz_noise.h"
 #include "hiprz_probe.h"
 #include "hiprz_smooth.h"
+#include "hiprz_field.h"
 #include "hiprz_order.h"
 #include "hiprz_query.h"
 
@@ -337,6 +338,15 @@ public:
     // every word comes back unchanged.  The bytes of Context.smooth_texels.  Waits for the stream; changes no frame.
     std::vector<Record> smoothTexels(const std::vector<hiprz_bake_point>& points, const std::vector<Record>& records, uint32_t width, uint32_t height,
                                      const hiprz_smooth_params& params);
+    // Probe fields (include/hiprz_field.h).  bakeVisibility: per probe an 8 x 8 octahedral map of the mean and the mean square of
+    // min(distance to the closest hit, reach) over the K rays of the sphere table (K, S), K >= 64, in the world of the last renderWorld
+    // call.  lookupField: the irradiance the probes of `grid` (their positions `probes`, records `sh` and — unless empty — visibility
+    // records `vis`, in the grid's C order) give every point of `points`, evaluated on the device; with `vis` a probe behind a wall does
+    // not leak.  The bytes of Context.bake_visibility and Context.lookup_field.  Wait for the stream; change no frame.
+    std::vector<hiprz_field_vis> bakeVisibility(const std::vector<hiprz_bake_point>& probes, float reach, uint32_t K = 256, uint32_t S = 4, uint32_t seed = 0);
+    std::vector<hiprz_field_result> lookupField(const hiprz_field_grid& grid, const std::vector<hiprz_bake_point>& probes, const std::vector<hiprz_probe_sh>& sh,
+                                                const std::vector<hiprz_field_vis>& vis, const std::vector<hiprz_bake_point>& points,
+                                                const hiprz_field_params& params = hiprz_field_params{0.0f, 0u, {0u, 0u}});
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -393,6 +403,9 @@ private:
     hiprz_light* lighter(uint32_t K, uint32_t S);  // m_light holding the disk table of (K, S)
     hiprz_smooth* m_smooth = nullptr;       // bound to m_ctx, created at the first smoothing
     hiprz_smooth* smoother();               // m_smooth, created when there is none
+    hiprz_field* m_field = nullptr;         // bound to m_ctx, created at the first bakeVisibility or lookupField; it holds the sphere table of (m_field_k, m_field_s)
+    uint32_t m_field_k = 0, m_field_s = 0;
+    hiprz_field* fielder();                 // m_field, created when there is none
     hiprz_probe* m_probe = nullptr;         // bound to m_ctx, created at the first bakeProbes; it holds the sphere table of (m_probe_k, m_probe_s) and the disk table
     uint32_t m_probe_k = 0, m_probe_s = 0, m_probe_light_k = 0, m_probe_light_s = 0;
     hiprz_gather* m_gather = nullptr;       // bound to m_ctx, created at the first gather; it holds the cosine table of (m_gather_k, m_gather_s)

@@ -152,6 +152,9 @@ class Context:
         if getattr(self, "_smooth", None) is not None:
             self._smooth.close()
             self._smooth = None
+        if getattr(self, "_field", None) is not None:
+            self._field.close()
+            self._field = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -693,30 +696,86 @@ class Context:
         return self._probe_with(directions, None, charts).samples(probes, seed, self.sync)
 
     def bake_probe_field(self, parts, width, height, albedo, emission, bounces, probes, directions=(64, 4), samples=(16, 4), seed=0, rings=2, sky=(0.0, 0.0, 0.0),
-                         near=1.0e-3, far=3.0e38, lights=None, probe_directions=(64, 4), direct=True, smooth=None):
+                         near=1.0e-3, far=3.0e38, lights=None, probe_directions=(64, 4), direct=True, smooth=None, visibility=None):
         """bake_bounce_atlas and, while the source of its last gather — albedo * (direct + indirect of the bounce before) + emission,
         dilated — is still on the device, bake_probes of `probes` from it: (direct, indirect, ring, sh), the first three what
         bake_bounce_atlas returns in every byte, sh of probe.sh_dtype in the shape of `probes`.  probe_directions: the probes' table, a
-        (K, S) pair for the sphere table or an (S, K, 4) array.  smooth: as for bake_bounce_atlas.  Waits for the stream; changes no frame."""
+        (K, S) pair for the sphere table or an (S, K, 4) array.  smooth: as for bake_bounce_atlas.  visibility: None, or a reach — then
+        bake_visibility of the probes (the table set on the fielder before, (256, 4) when none is, the same seed) is run while they are
+        on the device and its records (field.vis_dtype, the shape of `probes`) come back as a fifth item.  Waits for the stream; changes
+        no frame."""
         from . import _hiprt
         from . import gather as _gather
         from . import probe as _probe
         probes = _probe.Probe._probes(probes)
         p = self._probe_with(probe_directions, samples if direct else None, _gather.chart_tables(parts, getattr(self, "_n_instances", 0)))
         bufs = []
+        if visibility is None:
+            def then(source_ptr):
+                if probes.size == 0:
+                    return np.zeros(probes.shape, _probe.sh_dtype)
+                bufs.extend([_hiprt.DeviceBuffer.of(probes), _hiprt.DeviceBuffer(probes.size * _probe.sh_dtype.itemsize)])
+                p.bake_device(bufs[0].ptr, probes.size, source_ptr, width, height, bufs[1].ptr, seed, sky, lights, direct)
+                return lambda: bufs[1].download(probes.shape, _probe.sh_dtype)
+        else:
+            from . import field as _field
+            f = self._field_with(None if self.fielder().K else (256, 4))
+            seen = []
 
-        def then(source_ptr):
-            if probes.size == 0:
-                return np.zeros(probes.shape, _probe.sh_dtype)
-            bufs.extend([_hiprt.DeviceBuffer.of(probes), _hiprt.DeviceBuffer(probes.size * _probe.sh_dtype.itemsize)])
-            p.bake_device(bufs[0].ptr, probes.size, source_ptr, width, height, bufs[1].ptr, seed, sky, lights, direct)
-            return lambda: bufs[1].download(probes.shape, _probe.sh_dtype)
+            def then(source_ptr):
+                if probes.size == 0:
+                    seen.append(np.zeros(probes.shape, _field.vis_dtype))
+                    return np.zeros(probes.shape, _probe.sh_dtype)
+                bufs.extend([_hiprt.DeviceBuffer.of(probes), _hiprt.DeviceBuffer(probes.size * _probe.sh_dtype.itemsize), _hiprt.DeviceBuffer(probes.size * _field.vis_dtype.itemsize)])
+                p.bake_device(bufs[0].ptr, probes.size, source_ptr, width, height, bufs[1].ptr, seed, sky, lights, direct)
+                f.visibility_device(bufs[0].ptr, probes.size, bufs[2].ptr, seed, visibility)
+
+                def after():
+                    seen.append(bufs[2].download(probes.shape, _field.vis_dtype))
+                    return bufs[1].download(probes.shape, _probe.sh_dtype)
+                return after
 
         try:
-            return self._bake_bounce(parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, then, smooth)
+            baked = self._bake_bounce(parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, then, smooth)
+            return baked if visibility is None else baked + (seen[0],)
         finally:
             for b in bufs:
                 b.free()
+
+    # --- probe fields: a visibility map per probe and the leak-free lookup of a grid of probes on the device (include/hiprz_field.h) ---
+    def fielder(self):
+        """the context's field.Fielder, created at the first use (device-pointer calls: visibility_device, lookup_device)"""
+        from . import field as _field
+        if getattr(self, "_field", None) is None:
+            self._field = _field.Fielder(self._ctx)
+        return self._field
+
+    def _field_with(self, directions):
+        f = self.fielder()
+        if directions is not None and not (isinstance(directions, tuple) and directions == f.table):       # a sphere table already set is not set again
+            f.set_directions(directions)
+        return f
+
+    def bake_visibility(self, probes, directions=(256, 4), seed=0, reach=3.0e38):
+        """How far every probe of `probes` (an array of bake.point_dtype, as for bake_probes) sees in each direction: an array of
+        field.vis_dtype of the same shape — per texel of an 8 x 8 octahedral map in world axes the mean and the mean square of
+        min(distance to the closest hit, reach) over the probe's K rays, each ray weighted by the 32nd power of its cosine to the texel's
+        direction; `words` = (front-face hits, back-face hits, misses, K), words[3] = field.INVALID for an invalid probe.  directions: a
+        (K, S) pair for the sphere table, an (S, K, 4) array or None for the table set before; K >= 64.  The rays are bake_rays's for the
+        same table and seed.  reach: what a ray that hits nothing sees, and the cap of every distance — a few grid steps.  Waits for the
+        stream; changes no frame."""
+        return self._field_with(directions).visibility(probes, seed, reach)
+
+    def lookup_field(self, grid, probes, sh, points, vis=None, params=None):
+        """The irradiance a grid of baked probes gives every point of `points` (an array of bake.point_dtype: position and unit normal;
+        near and far are ignored), evaluated on the device: an array of field.result_dtype of the same shape — `rgb` in the units of a
+        lightmap texel, `word` the number of probes that took part (field.INVALID, and rgb 0, for an invalid point or when none did).
+        grid: field.grid_of(lo, hi, shape); probes and sh: the grid's probes (probe.grid) and their records in its C order; vis: their
+        bake_visibility records — each of the eight probes around a point is then weighted by a Chebyshev test of the point's distance
+        against what the probe saw in its direction, so that a probe behind a wall does not leak — or None for the plain trilinear
+        blend; params: field.params(bias=..., max_back=...), a dict of its keywords or None for its defaults.  Needs no uploaded scene.
+        Waits for the stream; changes no frame."""
+        return self.fielder().lookup(grid, probes, sh, points, vis, params)
 
     def pixel_rays(self):
         """(H, W) array of query.ray_dtype: the selected camera's pixel-centre rays, the ones the first pass, the guides and ray_cast walk"""
