@@ -84,7 +84,8 @@
  * is irradiance in the units of a lightmap texel.
  *
  * Left out on purpose:
- *   - probe placement: moving probes out of geometry; a probe inside geometry is only left out (max_back);
+ *   - probe placement: moving probes out of geometry is include/hiprz_place.h's, whose moved probes this lookup takes as they are; a
+ *     probe that still sits inside geometry is only left out (max_back);
  *   - a bilinear tap of the visibility map and maps larger than 8 x 8;
  *   - an irregular or sparse grid, and a grid streamed in parts;
  *   - blending the coefficients: the lookup evaluates each probe for the point's normal and blends irradiance.

@@ -93,7 +93,8 @@
  *   - bands above 2;
  *   - ringing windowing: the coefficients are the plain projection;
  *   - probe placement and visibility: a probe inside geometry sees back faces (+0), a probe behind a wall leaks through a plain
- *     interpolation — include/hiprz_field.h bakes a visibility map per probe and weights the blend by it;
+ *     interpolation — include/hiprz_field.h bakes a visibility map per probe and weights the blend by it, include/hiprz_place.h moves
+ *     probes out of geometry before either bake;
  *   - glossy transport, transmission and the scattering medium, as the gather leaves them out;
  *   - a device-side evaluation kernel: the evaluation is nine multiply-adds a shader writes itself; the lookup of a whole grid of
  *     probes for shaded points on the device is include/hiprz_field.h's.

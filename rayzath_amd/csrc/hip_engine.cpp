@@ -355,6 +355,7 @@ Engine::~Engine() {
     if (m_probe) hiprz_probe_destroy(m_probe);
     if (m_smooth) hiprz_smooth_destroy(m_smooth);
     if (m_field) hiprz_field_destroy(m_field);
+    if (m_place) hiprz_place_destroy(m_place);
     hiprz_destroy(m_ctx);
 }
 
@@ -656,6 +657,25 @@ std::vector<hiprz_field_vis> Engine::bakeVisibility(const std::vector<hiprz_bake
     return out;
 }
 
+std::vector<hiprz_bake_point> Engine::placeProbes(const std::vector<hiprz_bake_point>& probes, const hiprz_place_params& params, std::vector<hiprz_place_record>* records, uint32_t K,
+                                                  uint32_t S, uint32_t seed) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (!m_place)
+        if (const int rc = hiprz_place_create(&m_place, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_place_last_error(nullptr));
+    if (K != m_place_k || S != m_place_s) {  // the sphere table of (K, S), kept until another is asked for
+        std::vector<float> table(4 * size_t(K) * S);
+        if (const int rc = hiprz_probe_sphere_directions(K, S, table.data()); rc != HIPRZ_OK) throw Exception(rc, "placeProbes: K is not one of 64 .. 1024 (powers of two) or S is not in 1..64");
+        if (const int rc = hiprz_place_set_directions(m_place, table.data(), K, S); rc != HIPRZ_OK) throw Exception(rc, hiprz_place_last_error(m_place));
+        m_place_k = K, m_place_s = S;
+    }
+    std::vector<hiprz_bake_point> out(probes.size());
+    if (records) records->assign(probes.size(), hiprz_place_record{});
+    if (probes.empty()) return out;
+    if (const int rc = hiprz_place_probes_host(m_place, probes.data(), probes.size(), seed, &params, out.data(), records ? records->data() : nullptr); rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_place_last_error(m_place));
+    return out;
+}
+
 std::vector<hiprz_field_result> Engine::lookupField(const hiprz_field_grid& grid, const std::vector<hiprz_bake_point>& probes, const std::vector<hiprz_probe_sh>& sh,
                                                     const std::vector<hiprz_field_vis>& vis, const std::vector<hiprz_bake_point>& points, const hiprz_field_params& params) {
     std::lock_guard<std::mutex> lock(m_mutex);
@@ -811,6 +831,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_smooth = nullptr;
                 if (m_field) hiprz_field_destroy(m_field);
                 m_field = nullptr, m_field_k = m_field_s = 0;
+                if (m_place) hiprz_place_destroy(m_place);
+                m_place = nullptr, m_place_k = m_place_s = 0;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

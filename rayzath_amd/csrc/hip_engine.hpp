@@ -31,6 +31,7 @@
 #include "hiprz_probe.h"
 #include "hiprz_smooth.h"
 #include "hiprz_field.h"
+#include "hiprz_place.h"
 #include "hiprz_order.h"
 #include "hiprz_query.h"
 
@@ -347,6 +348,12 @@ public:
     std::vector<hiprz_field_result> lookupField(const hiprz_field_grid& grid, const std::vector<hiprz_bake_point>& probes, const std::vector<hiprz_probe_sh>& sh,
                                                 const std::vector<hiprz_field_vis>& vis, const std::vector<hiprz_bake_point>& points,
                                                 const hiprz_field_params& params = hiprz_field_params{0.0f, 0u, {0u, 0u}});
+    // Probe placement (include/hiprz_place.h): the probes moved out of geometry and away from the surface they hug, by the rays of the
+    // sphere table (K, S), K >= 64, in the world of the last renderWorld call; at most params.iterations moves, the offset within
+    // params.max_offset on every axis.  The moved probes, and in `records` (unless null) the offset, the state at the final position, the
+    // moves made and what the probe sees there.  The bytes of Context.place_probes.  Waits for the stream; changes no frame.
+    std::vector<hiprz_bake_point> placeProbes(const std::vector<hiprz_bake_point>& probes, const hiprz_place_params& params, std::vector<hiprz_place_record>* records = nullptr,
+                                              uint32_t K = 256, uint32_t S = 4, uint32_t seed = 0);
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -406,6 +413,8 @@ private:
     hiprz_field* m_field = nullptr;         // bound to m_ctx, created at the first bakeVisibility or lookupField; it holds the sphere table of (m_field_k, m_field_s)
     uint32_t m_field_k = 0, m_field_s = 0;
     hiprz_field* fielder();                 // m_field, created when there is none
+    hiprz_place* m_place = nullptr;         // bound to m_ctx, created at the first placeProbes; it holds the sphere table of (m_place_k, m_place_s)
+    uint32_t m_place_k = 0, m_place_s = 0;
     hiprz_probe* m_probe = nullptr;         // bound to m_ctx, created at the first bakeProbes; it holds the sphere table of (m_probe_k, m_probe_s) and the disk table
     uint32_t m_probe_k = 0, m_probe_s = 0, m_probe_light_k = 0, m_probe_light_s = 0;
     hiprz_gather* m_gather = nullptr;       // bound to m_ctx, created at the first gather; it holds the cosine table of (m_gather_k, m_gather_s)

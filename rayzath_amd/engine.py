@@ -155,6 +155,9 @@ class Context:
         if getattr(self, "_field", None) is not None:
             self._field.close()
             self._field = None
+        if getattr(self, "_place", None) is not None:
+            self._place.close()
+            self._place = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -696,20 +699,26 @@ class Context:
         return self._probe_with(directions, None, charts).samples(probes, seed, self.sync)
 
     def bake_probe_field(self, parts, width, height, albedo, emission, bounces, probes, directions=(64, 4), samples=(16, 4), seed=0, rings=2, sky=(0.0, 0.0, 0.0),
-                         near=1.0e-3, far=3.0e38, lights=None, probe_directions=(64, 4), direct=True, smooth=None, visibility=None):
+                         near=1.0e-3, far=3.0e38, lights=None, probe_directions=(64, 4), direct=True, smooth=None, visibility=None, place=None):
         """bake_bounce_atlas and, while the source of its last gather — albedo * (direct + indirect of the bounce before) + emission,
         dilated — is still on the device, bake_probes of `probes` from it: (direct, indirect, ring, sh), the first three what
         bake_bounce_atlas returns in every byte, sh of probe.sh_dtype in the shape of `probes`.  probe_directions: the probes' table, a
         (K, S) pair for the sphere table or an (S, K, 4) array.  smooth: as for bake_bounce_atlas.  visibility: None, or a reach — then
         bake_visibility of the probes (the table set on the fielder before, (256, 4) when none is, the same seed) is run while they are
-        on the device and its records (field.vis_dtype, the shape of `probes`) come back as a fifth item.  Waits for the stream; changes
-        no frame."""
+        on the device and its records (field.vis_dtype, the shape of `probes`) come back as a fifth item.  place: None, or
+        place.params(...) / place.params_for(grid, ...) (or a dict of params' keywords) — then place_probes (the table set on the
+        placer before, (256, 4) when none is, the same seed) moves the probes where they lie on the device first, sh and the visibility
+        records are baked at the moved positions, and the moved probes (the dtype and shape of `probes`) and their records
+        (place.record_dtype) come back as two more trailing items.  Waits for the stream; changes no frame."""
         from . import _hiprt
         from . import gather as _gather
         from . import probe as _probe
         probes = _probe.Probe._probes(probes)
         p = self._probe_with(probe_directions, samples if direct else None, _gather.chart_tables(parts, getattr(self, "_n_instances", 0)))
         bufs = []
+        if place is not None:
+            return self._bake_placed_field(p, place, parts, width, height, albedo, emission, bounces, probes, directions, samples, seed, rings, sky, near, far, lights, direct,
+                                           smooth, visibility)
         if visibility is None:
             def then(source_ptr):
                 if probes.size == 0:
@@ -741,6 +750,69 @@ class Context:
         finally:
             for b in bufs:
                 b.free()
+
+    def _bake_placed_field(self, p, place, parts, width, height, albedo, emission, bounces, probes, directions, samples, seed, rings, sky, near, far, lights, direct, smooth,
+                           visibility):
+        """bake_probe_field(place=): the probes are moved in their device buffer before the two bakes read it"""
+        from . import _hiprt
+        from . import field as _field
+        from . import place as _place
+        from . import probe as _probe
+        placer = self._place_with(None if self.placer().K else (256, 4))
+        f = None if visibility is None else self._field_with(None if self.fielder().K else (256, 4))
+        bufs, extra = [], []
+
+        def then(source_ptr):
+            if probes.size == 0:
+                extra.extend(([] if f is None else [np.zeros(probes.shape, _field.vis_dtype)]) + [probes.copy(), np.zeros(probes.shape, _place.record_dtype)])
+                return np.zeros(probes.shape, _probe.sh_dtype)
+            sizes = [_probe.sh_dtype.itemsize, _place.record_dtype.itemsize] + ([] if f is None else [_field.vis_dtype.itemsize])
+            bufs.extend([_hiprt.DeviceBuffer.of(probes)] + [_hiprt.DeviceBuffer(probes.size * size) for size in sizes])
+            placer.probes_device(bufs[0].ptr, probes.size, bufs[0].ptr, bufs[2].ptr, seed, place)
+            p.bake_device(bufs[0].ptr, probes.size, source_ptr, width, height, bufs[1].ptr, seed, sky, lights, direct)
+            if f is not None:
+                f.visibility_device(bufs[0].ptr, probes.size, bufs[3].ptr, seed, visibility)
+
+            def after():
+                if f is not None:
+                    extra.append(bufs[3].download(probes.shape, _field.vis_dtype))
+                extra.extend([bufs[0].download(probes.shape, probes.dtype), bufs[2].download(probes.shape, _place.record_dtype)])
+                return bufs[1].download(probes.shape, _probe.sh_dtype)
+            return after
+
+        try:
+            return self._bake_bounce(parts, width, height, albedo, emission, bounces, directions, samples, seed, rings, sky, near, far, lights, then, smooth) + tuple(extra)
+        finally:
+            for b in bufs:
+                b.free()
+
+    # --- probe placement: the probes of a grid moved out of geometry and away from the surface they hug (include/hiprz_place.h) ---
+    def placer(self):
+        """the context's place.Placer, created at the first use (device-pointer call: probes_device)"""
+        from . import place as _place
+        if getattr(self, "_place", None) is None:
+            self._place = _place.Placer(self._ctx)
+        return self._place
+
+    def _place_with(self, directions):
+        pl = self.placer()
+        if directions is not None and not (isinstance(directions, tuple) and directions == pl.table):       # a sphere table already set is not set again
+            pl.set_directions(directions)
+        return pl
+
+    def place_probes(self, probes, directions=(256, 4), seed=0, params=None):
+        """The probes of `probes` (an array of bake.point_dtype, as for bake_probes) moved out of geometry: (moved, records) — `moved` like
+        `probes` with new positions, `records` of place.record_dtype in the same shape: the offset, place.state(records) at the final
+        position (place.CLEAR, NEAR — a front face nearer than min_front — or INSIDE — more than max_back rays hit back faces), the
+        place.STUCK bit when a wanted move was not made, the moves made, the nearest front and back face and the counts of rays that hit
+        either; word = place.INVALID for an invalid probe, which is copied unchanged.  A probe INSIDE steps through the nearest back face
+        and half of min_front beyond, a probe NEAR steps along its most open ray; the offset never exceeds max_offset on any axis.
+        directions: a (K, S) pair for the sphere table, an (S, K, 4) array or None for the table set before; K >= 64.  The rays are
+        bake_rays's for the same table and seed from wherever the probe is.  params: place.params(...) or place.params_for(grid, ...), or a
+        dict of params' keywords.  Waits for the stream; changes no frame."""
+        if params is None:
+            raise TypeError("place_probes needs params: place.params(min_front, reach, max_offset) or place.params_for(grid, min_front, reach)")
+        return self._place_with(directions).probes(probes, seed, params)
 
     # --- probe fields: a visibility map per probe and the leak-free lookup of a grid of probes on the device (include/hiprz_field.h) ---
     def fielder(self):
