@@ -356,6 +356,7 @@ Engine::~Engine() {
     if (m_smooth) hiprz_smooth_destroy(m_smooth);
     if (m_field) hiprz_field_destroy(m_field);
     if (m_place) hiprz_place_destroy(m_place);
+    if (m_view) hiprz_view_destroy(m_view);
     hiprz_destroy(m_ctx);
 }
 
@@ -689,6 +690,26 @@ std::vector<hiprz_field_result> Engine::lookupField(const hiprz_field_grid& grid
     return out;
 }
 
+std::vector<hiprz_view_pixel> Engine::bakedView(const std::vector<Record>& source, uint32_t width, uint32_t height, const ChartMap& charts, const hiprz_view_field* field,
+                                                const float* sky, uint32_t filter, std::vector<float>* image) {
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (source.size() != size_t(width) * height) throw Exception(HIPRZ_ERR_INVALID, "bakedView: the source is not width x height records");
+    if (!m_view)
+        if (const int rc = hiprz_view_create(&m_view, m_ctx); rc != HIPRZ_OK) throw Exception(rc, hiprz_view_last_error(nullptr));
+    if (const int rc = hiprz_view_set_charts(m_view, charts.base.data(), uint32_t(charts.base.size()), charts.uv.data(), uint32_t(charts.uv.size())); rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_view_last_error(m_view));
+    if (m_camera_records.empty()) throw Exception(HIPRZ_ERR_STATE, "bakedView: no world has been rendered");
+    const hiprz_camera& cam = m_camera_records.back();  // the camera renderWorld left selected
+    std::vector<hiprz_view_pixel> out(size_t(cam.width) * cam.height);
+    if (image) image->assign(4u * out.size(), 0.0f);
+    if (out.empty()) return out;
+    const float black[3] = {0.0f, 0.0f, 0.0f};
+    const hiprz_view_params params{filter, {0u, 0u, 0u}};
+    if (const int rc = hiprz_view_pixels_host(m_view, source.data(), width, height, field, sky ? sky : black, &params, out.data(), image ? image->data() : nullptr); rc != HIPRZ_OK)
+        throw Exception(rc, hiprz_view_last_error(m_view));
+    return out;
+}
+
 std::vector<hiprz_gather_texel> Engine::gather(const std::vector<hiprz_bake_point>& points, const std::vector<Record>& source, uint32_t width, uint32_t height,
                                                const ChartMap& charts, uint32_t K, uint32_t S, uint32_t seed, const float* sky) {
     std::lock_guard<std::mutex> lock(m_mutex);
@@ -833,6 +854,8 @@ void Engine::renderWorld(World& world, const RenderConfig& cfg, bool /*block*/, 
                 m_field = nullptr, m_field_k = m_field_s = 0;
                 if (m_place) hiprz_place_destroy(m_place);
                 m_place = nullptr, m_place_k = m_place_s = 0;
+                if (m_view) hiprz_view_destroy(m_view);
+                m_view = nullptr;
                 hiprz_destroy(m_ctx);
                 m_ctx = several;
                 check(hiprz_set_mode(m_ctx, m_mode));

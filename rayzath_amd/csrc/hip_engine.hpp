@@ -32,6 +32,7 @@
 #include "hiprz_smooth.h"
 #include "hiprz_field.h"
 #include "hiprz_place.h"
+#include "hiprz_view.h"
 #include "hiprz_order.h"
 #include "hiprz_query.h"
 
@@ -354,6 +355,13 @@ public:
     // moves made and what the probe sees there.  The bytes of Context.place_probes.  Waits for the stream; changes no frame.
     std::vector<hiprz_bake_point> placeProbes(const std::vector<hiprz_bake_point>& probes, const hiprz_place_params& params, std::vector<hiprz_place_record>* records = nullptr,
                                               uint32_t K = 256, uint32_t S = 4, uint32_t seed = 0);
+    // Baked view (include/hiprz_view.h): the frame of the selected camera of the last renderWorld call, shaded from the width x height atlas
+    // `source` (what a texel sends on: albedo x (direct + indirect) + emission, composed and dilated) through `charts` and — for objects
+    // outside the atlas, unless `field` is null — from a probe field (lookupField's arguments, as host pointers) times the surface's colour.
+    // One 16-byte record per pixel, row-major: the RGB and kind << 28 | count; with `image` also the float4 (r, g, b, 1) per pixel.  The
+    // bytes of Context.view.  Waits for the stream; changes no frame.
+    std::vector<hiprz_view_pixel> bakedView(const std::vector<Record>& source, uint32_t width, uint32_t height, const ChartMap& charts, const hiprz_view_field* field = nullptr,
+                                            const float* sky = nullptr, uint32_t filter = HIPRZ_VIEW_NEAREST, std::vector<float>* image = nullptr);
     // The variance estimate on for noise() whatever setDenoise asks for (renderUntil sets it); a real change restarts accumulation.
     void setMeasuring(bool enabled);
     // Render to a noise target: renderWorld(sync = true) calls, each one batch of tracing.rpp passes, until EVERY pixel of the frame has an
@@ -415,6 +423,7 @@ private:
     hiprz_field* fielder();                 // m_field, created when there is none
     hiprz_place* m_place = nullptr;         // bound to m_ctx, created at the first placeProbes; it holds the sphere table of (m_place_k, m_place_s)
     uint32_t m_place_k = 0, m_place_s = 0;
+    hiprz_view* m_view = nullptr;           // bound to m_ctx, created at the first bakedView
     hiprz_probe* m_probe = nullptr;         // bound to m_ctx, created at the first bakeProbes; it holds the sphere table of (m_probe_k, m_probe_s) and the disk table
     uint32_t m_probe_k = 0, m_probe_s = 0, m_probe_light_k = 0, m_probe_light_s = 0;
     hiprz_gather* m_gather = nullptr;       // bound to m_ctx, created at the first gather; it holds the cosine table of (m_gather_k, m_gather_s)

@@ -158,6 +158,9 @@ class Context:
         if getattr(self, "_place", None) is not None:
             self._place.close()
             self._place = None
+        if getattr(self, "_view", None) is not None:
+            self._view.close()
+            self._view = None
         if self._ctx:
             self.lib.hiprz_destroy(self._ctx)
             self._ctx = C.c_void_p()
@@ -848,6 +851,79 @@ class Context:
         blend; params: field.params(bias=..., max_back=...), a dict of its keywords or None for its defaults.  Needs no uploaded scene.
         Waits for the stream; changes no frame."""
         return self.fielder().lookup(grid, probes, sh, points, vis, params)
+
+    # --- baked view: a frame of the selected camera shaded from a lit atlas and a probe field (include/hiprz_view.h) ---
+    def viewer(self):
+        """the context's view.View, created at the first use (device-pointer calls: pixels_device, samples_device)"""
+        from . import view as _view
+        if getattr(self, "_view", None) is None:
+            self._view = _view.View(self._ctx)
+        return self._view
+
+    def _view_with(self, charts):
+        v = self.viewer()
+        if charts is not None:
+            v.set_charts(*charts)
+        return v
+
+    def view(self, source, width, height, charts, field=None, sky=(0.0, 0.0, 0.0), params=None, rgba8=False):
+        """The selected camera's frame of the baked scene: an (H_c, W_c) array of view.pixel_dtype — `rgb`, and `word` = kind << 28 |
+        count.  Every pixel casts its pixel-centre ray (pixel_rays) to its closest hit (trace).  A front-face hit on an object of the
+        chart map reads the width x height atlas `source` — 16-byte records, what a texel sends on (lit_source) — at the hit: kind
+        view.ATLAS, count the taps used; params: view.params(filter="nearest" | "bilinear"), the filter's name or None for nearest, the
+        texel gather reads.  A front-face hit on an object outside the atlas reads the probe field `field` = (grid, probes, sh,
+        vis_or_None, field_params_or_None), the arguments of lookup_field, at the hit for the hit's normal, times the surface's colour,
+        plus colour x emission on an emitter: kind view.FIELD, count the probes.  view.NONE (rgb 0) where neither has a value, view.SKY
+        (`sky`) where the ray hits nothing, view.BACK (rgb 0) on a back face.  charts: (base, uv) of gather.chart_tables(parts,
+        n_instances), or None for the map set before (a map equal to the one set is not uploaded again).  rgba8: also return the (H_c, W_c, 4) uint8 frame tonemap_image makes of the
+        float image under the selected camera's exposure.  Waits for the stream; changes no frame."""
+        from . import _hiprt
+        from . import view as _view
+        v = self._view_with(charts)
+        source = np.ascontiguousarray(source)
+        if source.dtype.itemsize != 16 or source.size != width * height:
+            raise TypeError("source must be width*height records of 16 bytes")
+        arrays = None if field is None else _view.field_arrays(field)
+        shape, n = (self.height, self.width), max(self.width * self.height, 1)
+        self.sync()  # (makes the head device the current one: the buffers below are allocated there)
+        bufs = [_hiprt.DeviceBuffer.of(source), _hiprt.DeviceBuffer(n * 16)]
+        try:
+            image = rgba = None
+            if rgba8:
+                image, rgba = _hiprt.DeviceBuffer(n * 16), _hiprt.DeviceBuffer(n * 4)
+                bufs += [image, rgba]
+            on_device = None
+            if arrays is not None:
+                grid, probes, sh, vis, fp = arrays
+                held = [_hiprt.DeviceBuffer.of(probes), _hiprt.DeviceBuffer.of(sh)] + ([] if vis is None else [_hiprt.DeviceBuffer.of(vis)])
+                bufs += held
+                on_device = (grid, held[0].ptr, held[1].ptr, None if vis is None else held[2].ptr, probes.size, fp)
+            v.pixels_device(bufs[0].ptr, width, height, bufs[1].ptr, None if image is None else image.ptr, on_device, sky, params)
+            if rgba8:
+                self.tonemap_image(image.ptr, rgba.ptr)
+            self.sync()
+            pixels = bufs[1].download(shape, _view.pixel_dtype)
+            return (pixels, rgba.download(shape + (4,), np.uint8)) if rgba8 else pixels
+        finally:
+            for b in bufs:
+                b.free()
+
+    def view_samples(self, charts=None):
+        """What view walks for the selected camera's pixels under the chart map set before (or `charts`): gather.sample_dtype of shape
+        (H_c, W_c) — the chart id under the pixel's closest hit or one of gather.MISS / UNMAPPED / BACK / INVALID_RAY, the hit's
+        barycentric weights of vertices 2 and 3, and its distance."""
+        return self._view_with(charts).samples((self.height, self.width), self.sync)
+
+    def lit_source(self, direct, indirect, albedo, emission=None, rings=2):
+        """The source of view from what bake_bounce_atlas returns: albedo * (direct + indirect) + emission per texel (the gather's
+        compose) and `rings` rings of gutter dilation on the atlas built last.  direct and indirect: (H, W) 16-byte records (indirect may
+        be None); albedo and emission as for bake_bounce_atlas.  (H, W) records of gather.record_dtype."""
+        from . import gather as _gather
+        direct = np.ascontiguousarray(direct)
+        albedo = _gather.records(albedo, direct.shape)
+        emission = None if emission is None else _gather.records(emission, direct.shape)
+        composed = self.gatherer().compose(direct, indirect, albedo, emission, self.sync)
+        return self.atlas().dilate(composed, rings)[0].view(_gather.record_dtype)
 
     def pixel_rays(self):
         """(H, W) array of query.ray_dtype: the selected camera's pixel-centre rays, the ones the first pass, the guides and ray_cast walk"""
