@@ -1,6 +1,6 @@
 """The world of tests/test_gather_gpu.py and its atlas, with the float64 geometry the tests hold the device to: the floor, cube and sphere
 of tests/test_light_gpu.py (rebuilt here) plus one wall, a 64 x 48 atlas in which floor, cube and wall each have a rectangle of their own
-and the sphere has none, the world-space triangles in float64, a float64 closest hit over them (for the CPU check of the boundary cap in
+and the sphere has none (the cube's six faces each in a cell of their own inside the cube's rectangle), the world-space triangles in float64, a float64 closest hit over them (for the CPU check of the boundary cap in
 tests/test_gather_reference.py) and the float64 barycentrics of a known hit.
 
 THE WALL is the unit plane stood upright, 2.1 wide and 1.4 tall, in front of the back third of the floor with its front to the camera and
@@ -16,6 +16,11 @@ FLOOR, CUBE, SPHERE, WALL = 0, 1, 2, 3
 # (u0, v0, u1, v1) in atlas units: the mesh's own UVs, which lie in [0, 1]^2, are scaled into the rectangle.  No edge of a rectangle lies on
 # a texel boundary of a 64 x 48 atlas.
 RECTS = {FLOOR: (0.03, 0.04, 0.47, 0.96), CUBE: (0.53, 0.04, 0.97, 0.46), WALL: (0.53, 0.54, 0.97, 0.96)}
+# The cube's six faces (f = triangle // 2) each have a cell of their own, 3 x 2 in the cube's rectangle, with a gutter between cells given
+# here as a share of the rectangle: 0.1 x 28.16 = 2.8 texels across and 0.14 x 20.16 = 2.8 texels down at 64 x 48, more than the two rings
+# of dilation the tests use, so that a ring-1 texel next to a cell holds that cell's face.  No edge of a cell lies within 0.05 texel of a
+# texel boundary or of a texel centre of a 64 x 48 atlas (tests/test_bake_meaning.py).
+CELLS, GUTTER = (3, 2), (0.1, 0.14)
 SPOT = dict(position=(1.5, 4.0, -1.0), direction=(-0.3, -1.0, 0.25), color=(255, 240, 220, 255), size=0.35, emission=60.0, beam_angle=0.8)
 DIRECT = dict(direction=(-0.25, -1.0, 0.45), color=(255, 255, 240, 255), emission=4.0, angular_size=0.15)
 
@@ -44,13 +49,29 @@ def world(moved=False, geometry=True, lights=True):
     return w
 
 
-def parts(w):
-    """the atlas's parts: floor, cube and wall, each mesh's own UVs scaled into its rectangle; the sphere is left out on purpose"""
+def cube_cell(face):
+    """(u0, v0, u1, v1) of a cube face's cell in the unit square the cube's rectangle scales: column face % 3, row face // 3"""
+    c, r = face % CELLS[0], face // CELLS[0]
+    cw, ch = (1.0 - (CELLS[0] - 1) * GUTTER[0]) / CELLS[0], (1.0 - (CELLS[1] - 1) * GUTTER[1]) / CELLS[1]
+    return c * (cw + GUTTER[0]), r * (ch + GUTTER[1]), c * (cw + GUTTER[0]) + cw, r * (ch + GUTTER[1]) + ch
+
+
+def parts(w, overlapping=False):
+    """the atlas's parts: floor, cube and wall, each mesh's own UVs scaled into its rectangle; the sphere is left out on purpose.  The cube's
+    own UVs lay every face over the whole unit square, so each face f = triangle // 2 is first scaled into its own cell (cube_cell): no
+    texel is claimed twice.  overlapping=True leaves the cube's UVs as they are: six faces on the same texels, of which the lowest id
+    owns each (include/hiprz_atlas.h), so that five faces read the first one's texels."""
     out = []
     for instance, (u0, v0, u1, v1) in RECTS.items():
         tris = atlas.charts(w.instances[instance].mesh)
         for k in (1, 2, 3):
             assert (tris[f"u{k}"] >= 0).all() and (tris[f"u{k}"] <= 1).all() and (tris[f"v{k}"] >= 0).all() and (tris[f"v{k}"] <= 1).all()
+        if instance == CUBE and not overlapping:
+            assert len(tris) == 2 * CELLS[0] * CELLS[1]
+            cell = np.array([cube_cell(t // 2) for t in range(len(tris))], F)
+            for k in (1, 2, 3):
+                tris[f"u{k}"], tris[f"v{k}"] = cell[:, 0] + (cell[:, 2] - cell[:, 0]) * tris[f"u{k}"], cell[:, 1] + (cell[:, 3] - cell[:, 1]) * tris[f"v{k}"]
+        for k in (1, 2, 3):
             tris[f"u{k}"], tris[f"v{k}"] = F(u0) + F(u1 - u0) * tris[f"u{k}"], F(v0) + F(v1 - v0) * tris[f"v{k}"]
         out.append((instance, tris))
     return out

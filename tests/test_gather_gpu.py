@@ -26,10 +26,10 @@ of floor, cube and wall scaled into a rectangle each; the sphere is in no part.
 
 MEASURED ON MI355X: 53 cases in 3.0 s beside the session's build fixture, slowest case 0.8 s (cases 1 - 3 on tree 0, which also makes the
 points), then 0.7 s (the C++ host: it compiles a program).  Per tree, cases 1 - 3: 574 080 rays byte-equal in t and id to the query's hits,
-2 884 of them back-face hits, 131 179 texels equal to the float64 reconstruction and 564 (0.43 %) on a boundary left out, every texel
+2 884 of them back-face hits, 131 223 texels equal to the float64 reconstruction and 520 (0.39 %) on a boundary left out, every texel
 bit-equal to the restatement, all four mutants caught; identical figures on trees 0 and 3.  Case 4: 35 of 64 and 567 of 1 024 rays reach
-the square, the float64 estimator's counts exactly.  Case 8: 12 floor texels before the wall gather R 0.205 G 0.138 from the red wall,
-R 0.198 G 0.189 from a grey one.  C++: 690 points, one invalid, 2 296 rays read a texel, 8 006 missed.
+the square, the float64 estimator's counts exactly.  Case 8: 12 floor texels before the wall gather R 0.064 G 0.004 from the red wall,
+R 0.057 G 0.055 from a grey one (the cube's faces in cells of their own: its sides no longer send on the top face's light).  C++: 690 points, one invalid, 2 282 rays read a texel, 8 006 missed.
 """
 import ctypes as C
 import os

@@ -153,7 +153,7 @@ def test_the_boundary_cap_of_the_gpu_tests_world_holds_in_float64():
     most 1 % of them.  That the atlas size and the rectangles of tests/gather_world.py allow this is shown here without a device: the
     hemisphere rays (tests/bake_reference.py, K = 64, three sets) of a 32 x 24 grid of floor points and of a 16 x 12 grid of points on
     the wall's front, walked in float64 over the world's 64 triangles.  Measured: 7.7 % of the floor's 49 152 rays and 50 % of the
-    wall's 12 288 land on a chart (the floor sees mostly sky); of those 0.32 % and 0.49 % lie on a boundary; 2.5 % of the floor's rays hit
+    wall's 12 288 land on a chart (the floor sees mostly sky); of those 0.34 % and 0.60 % lie on a boundary (the cube's faces in cells of their own); 2.5 % of the floor's rays hit
     a back face (the wall's)."""
     import bake_reference as BR
     import gather_world as GW
